@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """bench.py -- MeMOTR per-frame hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload msda|train]
+    python bench.py --gpus N --steps K --warmup W [--workload msda|train|infer] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0 (contract in the task description).  Workloads:
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` (wall time of one
+timed step) plus the workload's own counters.  Workloads:
 
   msda   (kernel path) one step = the MSDeformAttn work of one 800x1333 training frame:
          6 encoder calls (Lq = S = 22323) + 6 decoder calls (Lq = 300 + n_track), forward and
@@ -14,7 +15,13 @@ Prints ONE JSON line on rank 0 (contract in the task description).  Workloads:
          ~n-track live tracks.  value = frames/s.
 
 Every rank works on its own synthetic frame (clips shard by rank; no data-path collective), so
-scaling is "weak".  The JSON carries
+scaling is "weak".  A plain run sets up, warms up, times the steps and prints the line.
+
+--dump-outputs DIR  after the timed steps, writes what the last one computed as DIR/<name>.npy (float32 / float64; a
+                    fixed, seeded sample of the larger arrays, DUMP_SAMPLE elements each): two builds run with the same
+                    arguments get the same inputs and can be compared output for output.
+--full              also measures what the headline figure does not need, in the same process after the timed steps;
+                    the JSON then carries
   roofline      for the dominant kernel (encoder-shape fused forward, what the model launches): algorithmic bytes
                  / average launch duration, measured with HIP events on the launch stream; `traffic` =
                 measured fabric bytes (profiles/traffic.json, only if measured on this kernel at these sources)
@@ -23,7 +30,8 @@ scaling is "weak".  The JSON carries
   roofline_bf16                     (--dtype bf16) the bf16-storage forward on its own bytes
   kernels       launch times / kernel names of the encoder- and decoder-shape calls, both distributions
   cpu_baseline  the reference's pure-PyTorch fallback formulation (oracle.grid_sample_forward, a port
-                of models/ops/functions/ms_deform_attn_func.py:44-64) on the host cores, rank 0, N=1.
+                of models/ops/functions/ms_deform_attn_func.py:44-64) on the host cores, rank 0, N=1
+                (--no-cpu-baseline: without it).
 """
 from __future__ import annotations
 
@@ -47,7 +55,10 @@ import torch  # noqa: E402
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBPS = 8000.0  # MI355X spec
+# --dump-outputs: elements kept of an array larger than this (a fixed, seeded sample), and the cap on the whole dump
+DUMP_SAMPLE = 1 << 21
+DUMP_MAX_BYTES = 64_000_000
 
 
 def parse_args():
@@ -58,7 +69,11 @@ def parse_args():
     ap.add_argument("--workload", default=os.environ.get("MEMOTR_BENCH_WORKLOAD", "train"))
     ap.add_argument("--dist", default="encoder_like", choices=["encoder_like", "uniform"])
     ap.add_argument("--n-track", type=int, default=20, help="track queries carried into the frame (Lq = 300 + n)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel rooflines, the GEMM table and the CPU baseline (rank 0, after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores")
     # BASELINE.json configs 4 / 5 (secondary; the default line is config 2: DanceTrack, fp32, no checkpointing)
@@ -68,7 +83,10 @@ def parse_args():
     ap.add_argument("--use-checkpoint", action="store_true", help="activation checkpointing (CHECKPOINT_LEVEL 2)")
     ap.add_argument("--clip-len", type=int, default=0, help="0 = longest clip of the config")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="bf16 = autocast extension (config 5)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launcher_argv(n_gpus, script_argv, port=None):
@@ -92,7 +110,8 @@ def device_count():
 
 def self_launch_if_needed(args, script_argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): check the device count, then
-    replace this process by the N-rank launch.  Rank 0 of that launch prints the one JSON line to the same stdout.
+    run the N-rank launch as a child process and exit with its status.  Rank 0 of that launch prints the one JSON line
+    to the same stdout.
     MEMOTR_BENCH_DRY_LAUNCH=1 prints the launch command instead of running it."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
@@ -108,7 +127,8 @@ def self_launch_if_needed(args, script_argv):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC only on these hosts (RCCL across processes)
     env.setdefault("OMP_NUM_THREADS", "1")                # the launcher would set it anyway; ranks re-size their pools
     sys.stdout.flush()
-    os.execvpe(argv[0], argv, env)
+    import subprocess
+    raise SystemExit(subprocess.call(argv, env=env))
 
 
 def init_dist(n_gpus):
@@ -131,6 +151,31 @@ def barrier(world):
         import torch.distributed as dist
         dist.barrier()
     torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 if it is float64 and float32 otherwise.  An array of
+    more than DUMP_SAMPLE elements is represented by DUMP_SAMPLE of them, one from each of DUMP_SAMPLE equal slices of
+    its flattened order at an offset drawn from a generator seeded with the name: the same elements on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(a)
+        a = a.detach().reshape(-1)
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        n = a.numel()
+        if n > DUMP_SAMPLE:
+            stride = n // DUMP_SAMPLE
+            rng = np.random.default_rng(sum(map(ord, name)))
+            idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_SAMPLE)
+            a = a[torch.from_numpy(idx).to(a.device)]
+        v = a.cpu().numpy()
+        total += v.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 class MsdaCall:
@@ -531,7 +576,9 @@ def run_msda(args, rank, world):
 
     result = None
     if rank == 0:
-        k = kernel_lines(args, enc, dec)
+        if args.dump_outputs:       # (the step's last calls: the decoder's and the encoder's backward on these buffers)
+            dump_outputs(args.dump_outputs, {"enc_out": enc.out, "enc_grad_value": enc.gv, "enc_grad_proj": enc.gp,
+                                             "dec_out": dec.out, "dec_grad_value": dec.gv, "dec_grad_proj": dec.gp})
         result = {
             "metric": "msda_path_frames_per_sec", "value": world * args.steps / dt, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -540,10 +587,11 @@ def run_msda(args, rank, world):
                                    "800x1333 pyramid, M=8 D=32 L=4 P=4, bs=1/GPU" % (300 + args.n_track),
                        "loc_dist": args.dist, "parallelism": f"dp{world}"},
         }
-        result.update(k)
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline_msda(args, dict(dist=args.dist, seed=3),
-                                                       dict(dist=args.dist, seed=103, n_queries=300 + args.n_track))
+        if args.full:
+            result.update(kernel_lines(args, enc, dec))
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline_msda(args, dict(dist=args.dist, seed=3),
+                                                           dict(dist=args.dist, seed=103, n_queries=300 + args.n_track))
     return result
 
 
@@ -574,7 +622,11 @@ def run_infer(args, rank, world):
         res = model(frame=tensor_list_to_nested_tensor([frames[0]]).to(dev), tracks=tracker.tracks)
         best = logits_to_scores(res["pred_logits"])[0, :len(res["det_query_embed"])].max(-1).values
     n_track = max(1, min(args.n_track, best.numel()))
-    tracker.tracker.det_score_thresh = float(best.topk(n_track).values[-1])
+    top = best.topk(min(n_track + 1, best.numel())).values
+    # (half way to the next score: the frame-0 step below runs the model again, and a threshold ON the n-th score let
+    #  that detection in or out by the last bits of its second evaluation -- n_track or n_track - 1 tracks, run to run)
+    tracker.tracker.det_score_thresh = float(top[n_track - 1] + top[n_track]) / 2 if top.numel() > n_track \
+        else float(top[-1])
     tracker.tracker.track_score_thresh = 0.0
     tracker.step(frames[0], hw[0], hw[1])
     tracker.tracker.det_score_thresh = 2.0            # no further births: the live set stays at n_track
@@ -599,6 +651,9 @@ def run_infer(args, rank, world):
     dt = float(t.item())
     if rank != 0:
         return None
+    if args.dump_outputs:           # the last frame's reportable tracks, as the tracker hands them to its caller
+        dump_outputs(args.dump_outputs, {"track_ids": out.ids.double(), "track_labels": out.labels.double(),
+                                         "track_scores": out.scores, "track_area": out.area, "track_boxes": out.boxes})
     return {
         "metric": "infer_frames_per_sec", "value": world * args.steps / dt, "unit": "frames/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -616,6 +671,34 @@ def _infer_graph_stats(core) -> dict:
     e, d = core.infer_graphs().encode, core.transformer.decoder.infer_graphs().decode
     return {"encode": {"captures": e.captures, "replays": e.replays, "eager": e.eager, "failed": e.failed},
             "decoder": {"captures": d.captures, "replays": d.replays, "eager": d.eager, "failed": d.failed}}
+
+
+def dump_train_outputs(out_dir, loss, loss_dict, model):
+    """What a train step hands its caller: the loss, its terms (sorted by name) and the parameters after the update
+    (run_train: the dumped step starts from the same state in every run)."""
+    terms = [loss_dict[k] if torch.is_tensor(loss_dict[k]) else torch.tensor(float(loss_dict[k]))
+             for k in sorted(loss_dict)]
+    params = torch.cat([p.detach().reshape(-1).float() for p in model.parameters() if p.requires_grad])
+    dump_outputs(out_dir, {"loss": loss.reshape(1),
+                           "loss_terms": torch.stack([t.detach().float().reshape(()).cpu() for t in terms]),
+                           "params": params})
+
+
+def use_miopen_db(name):
+    """Point MIOpen's user db (find results, tuned solver settings) at a private copy of memotr_amd/tuning/<name>, unless
+    MIOPEN_USER_DB_PATH is set already: MIOpen adds the problems it had no record for to that db, and the copy keeps
+    those writes out of the repository.  Read by MIOpen at its first convolution."""
+    import atexit
+    import shutil
+    import tempfile
+    src = os.path.join(ROOT, "memotr_amd", "tuning", name)
+    if "MIOPEN_USER_DB_PATH" in os.environ or not os.path.isdir(src):
+        return
+    dst = tempfile.mkdtemp(prefix="memotr_miopen_db_")
+    atexit.register(shutil.rmtree, dst, True)
+    for f in os.listdir(src):                   # (contents only: the copy stays writable whatever the checkout's modes)
+        shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+    os.environ["MIOPEN_USER_DB_PATH"] = dst
 
 
 def frame_size(args):
@@ -691,7 +774,7 @@ def main():
         result = run_msda(args, rank, world)
     elif args.workload == "infer":
         result = run_infer(args, rank, world)
-        if rank == 0:
+        if rank == 0 and args.full:
             k = run_msda_kernels_only(args)
             result.update({n: v for n, v in k.items() if n.startswith(("roofline", "kernels"))})
             if world == 1 and not args.no_cpu_baseline:
@@ -710,12 +793,15 @@ def main():
             # the find results of this pyramid (fp32 and bf16) measured on MI355X travel with the package: MIOpen
             # answers from its user find-db instead of benchmarking every solver again (9 minutes -> the compile time
             # of the picked kernels)
-            db = os.path.join(ROOT, "memotr_amd", "tuning", "miopen_db")
-            if os.path.isdir(db):
-                os.environ.setdefault("MIOPEN_USER_DB_PATH", db)
+            use_miopen_db("miopen_db")
+        else:
+            # ... and those of the default pyramid's fp32 step: MIOpen's (non-exhaustive) find of its first step costs
+            # ~20 s of solver compiles and timings in a process whose per-user caches are cold, ~3 s with the records
+            use_miopen_db("miopen_db_800x1333")
         result = run_train(args, rank, world, clip_len=args.clip_len or max(cfg["SAMPLE_LENGTHS"]), height=hw[0],
-                           width=hw[1], config=cfg, dtype=args.dtype)
-        if rank == 0:   # the kernel roofline and the CPU fallback baseline ride along on rank 0
+                           width=hw[1], config=cfg, dtype=args.dtype,
+                           collect=(lambda **o: dump_train_outputs(args.dump_outputs, **o)) if args.dump_outputs else None)
+        if rank == 0 and args.full:   # the kernel roofline and the CPU fallback baseline ride along on rank 0
             k = run_msda_kernels_only(args)
             result.update({n: v for n, v in k.items() if n.startswith(("roofline", "kernels"))})
             if args.config == "dancetrack" and not args.use_checkpoint and isinstance(result.get("kernels"), dict):

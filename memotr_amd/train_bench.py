@@ -40,7 +40,12 @@ def load_gemm_tuning() -> int:
 
 
 def run_train(args, rank: int, world: int, clip_len: int = None, height: int = 800, width: int = 1333,
-              n_gts: int = 10, config: dict = None, dtype: str = "f32"):
+              n_gts: int = 10, config: dict = None, dtype: str = "f32", collect=None):
+    """``collect``: called on rank 0 after the timed steps with what the last one computed -- ``loss``, ``loss_dict``
+    and ``model`` (its parameters as that step's optimizer update left them).  With ``collect`` the last timed step
+    starts from the state the warm-up started from (parameters, optimizer, random generators), so that its inputs are
+    the same in every run: the steps before it differ from run to run by the order of float atomics, and a training
+    run amplifies that step after step.  The restore is not timed."""
     from .configs import dancetrack_config
     from .engine import build_optimizer, clip_forward_backward, clip_to_device, make_synthetic_clip, optimizer_step
     from .models import build_model
@@ -78,27 +83,35 @@ def run_train(args, rank: int, world: int, clip_len: int = None, height: int = 8
     def step():
         if dtype == "bf16":     # extension: bf16 GEMMs/convs/value under autocast, fp32 master weights and optimizer
             with torch.autocast("cuda", dtype=torch.bfloat16):
-                loss, _ = clip_forward_backward(model, criterion, batch, dev, use_dab=cfg["USE_DAB"])
+                loss, loss_dict = clip_forward_backward(model, criterion, batch, dev, use_dab=cfg["USE_DAB"])
         else:
-            loss, _ = clip_forward_backward(model, criterion, batch, dev, use_dab=cfg["USE_DAB"])
+            loss, loss_dict = clip_forward_backward(model, criterion, batch, dev, use_dab=cfg["USE_DAB"])
         optimizer_step(model, optimizer, cfg["CLIP_MAX_NORM"])
-        return loss
+        return loss, loss_dict
 
     def barrier():
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    start = _train_state(model, optimizer, dev) if collect is not None else None
     for _ in range(args.warmup):
         step()
     barrier()
     t0 = time.perf_counter()
     cpu0 = time.process_time()       # CPU time of this PROCESS, all its threads (launch thread, autograd's, torch's pool)
-    for _ in range(args.steps):
-        loss = step()
+    paused, paused_cpu = 0.0, 0.0
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            barrier()
+            p0, pc0 = time.perf_counter(), time.process_time()
+            _restore_train_state(model, optimizer, dev, start)
+            barrier()
+            paused, paused_cpu = time.perf_counter() - p0, time.process_time() - pc0
+        loss, loss_dict = step()
     barrier()
-    dt = time.perf_counter() - t0
-    host_ms = (time.process_time() - cpu0) / args.steps * 1e3
+    dt = time.perf_counter() - t0 - paused
+    host_ms = (time.process_time() - cpu0 - paused_cpu) / args.steps * 1e3
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     per_rank = [dt / args.steps * 1e3]
     per_rank_host = [host_ms]
@@ -120,7 +133,7 @@ def run_train(args, rank: int, world: int, clip_len: int = None, height: int = 8
     n_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
     from .utils.host import cpu_quota
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
-    return {
+    result = {
         "metric": "train_frames_per_sec", "value": world * clip_len * args.steps / dt, "unit": "frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
@@ -139,6 +152,41 @@ def run_train(args, rank: int, world: int, clip_len: int = None, height: int = 8
         "cpu_quota_per_rank": cpu_quota() / max(1, local_world), "torch_threads": torch.get_num_threads(),
         "decoder_graphs": _graph_stats(model)["captures"], "decoder_graph_stats": _graph_stats(model),
     }
+    if collect is not None:
+        collect(loss=loss, loss_dict=loss_dict, model=getattr(model, "module", model))
+    return result
+
+
+def _train_state(model, optimizer, dev) -> dict:
+    """What a clip train step reads besides its batch: parameters and buffers (copies), the optimizer's state and the
+    random generators the model and the criterion draw from."""
+    import random
+
+    import numpy as np
+    with torch.no_grad():
+        tensors = [t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
+    return {"tensors": tensors, "optimizer": {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+                                               for p, st in optimizer.state.items()},
+            "random": random.getstate(), "numpy": np.random.get_state(), "torch": torch.get_rng_state(),
+            "cuda": torch.cuda.get_rng_state(dev)}
+
+
+def _restore_train_state(model, optimizer, dev, state: dict) -> None:
+    """Back to ``state`` (_train_state), in place: the captured hipGraphs keep reading the same tensors."""
+    import random
+
+    import numpy as np
+    with torch.no_grad():
+        for t, v in zip(list(model.parameters()) + list(model.buffers()), state["tensors"]):
+            t.copy_(v)
+    optimizer.state.clear()
+    for p, st in state["optimizer"].items():
+        optimizer.state[p] = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+    optimizer.zero_grad()
+    random.setstate(state["random"])
+    np.random.set_state(state["numpy"])
+    torch.set_rng_state(state["torch"])
+    torch.cuda.set_rng_state(state["cuda"], dev)
 
 
 def _graph_stats(model) -> dict:

@@ -1,5 +1,6 @@
 import glob
 import os
+import re
 import sys
 
 # ROCm 7.2: with the runtime's AQL-packet capture on (the default) a MEMSET node of a replayed hipGraph is not ordered
@@ -32,13 +33,55 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+# A fixture is <name>.npz plus, when its arrays do not fit one file of GOLDEN_PART_BYTES, <name>.1.npz, <name>.2.npz, ...
+GOLDEN_PART_BYTES = 960_000
+_PART = re.compile(r"\.[0-9]+\.npz$")
+
+
 def golden_cases(pattern="msda_*.npz"):
-    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, pattern)))
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, pattern)) if not _PART.search(p))
+
+
+def load_npz(path):
+    """Every array of the fixture ``path`` (<name>.npz) and of its parts <name>.<i>.npz."""
+    stem = path[:-4]
+    parts = sorted(glob.glob(glob.escape(stem) + ".[0-9]*.npz"), key=lambda p: int(p[len(stem) + 1:-4]))
+    arrays = {}
+    for p in [path] + [p for p in parts if _PART.search(p)]:
+        with np.load(p) as z:
+            arrays.update({k: z[k] for k in z.files})
+    return arrays
+
+
+def save_npz(path, **arrays):
+    """np.savez_compressed of ``arrays`` as <name>.npz and, past GOLDEN_PART_BYTES, parts <name>.1.npz, ... (arrays
+    whole, in order; one array per file at most when it is larger on its own).  load_npz reads them back."""
+    import io
+    stem = path[:-4]
+    for p in glob.glob(glob.escape(stem) + ".[0-9]*.npz"):
+        if _PART.search(p):
+            os.remove(p)
+
+    def packed(group):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **group)
+        return buf.getvalue()
+
+    files, group, data = [], {}, packed({})
+    for k, v in arrays.items():
+        trial = packed(dict(group, **{k: v}))
+        if group and len(trial) > GOLDEN_PART_BYTES:
+            files.append(data)
+            group, trial = {}, packed({k: v})
+        group[k], data = v, trial
+    files.append(data)
+    for i, data in enumerate(files):
+        with open(path if i == 0 else f"{stem}.{i}.npz", "wb") as f:
+            f.write(data)
 
 
 def load_golden(name):
-    with np.load(os.path.join(GOLDEN_DIR, name + ".npz")) as z:
-        return {k: z[k] for k in z.files}
+    return load_npz(os.path.join(GOLDEN_DIR, name + ".npz"))
 
 
 @pytest.fixture(scope="session")

@@ -32,6 +32,8 @@ import torch
 
 REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(OUT))              # tests/: conftest.save_npz, fixtures split below 1 MiB a file
+from conftest import save_npz  # noqa: E402
 
 
 def import_reference_core():
@@ -107,7 +109,7 @@ def main():
             core, 15, N=1, M=4, D=64, Lq=33, P=4, shapes=[(9, 12), (5, 6)], dtype=dt, loc_lo=-0.1, loc_hi=1.1,
             value_scale=1.0)
     for cname, arrs in cases.items():
-        np.savez_compressed(os.path.join(OUT, f"msda_{cname}.npz"), **arrs)
+        save_npz(os.path.join(OUT, f"msda_{cname}.npz"), **arrs)
         print(cname, {k: v.shape for k, v in arrs.items() if k in ("value", "loc", "out")})
 
 

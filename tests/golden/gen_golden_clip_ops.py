@@ -28,6 +28,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gen_golden_model import install_stubs  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(OUT))              # tests/: conftest.save_npz, fixtures split below 1 MiB a file
+from conftest import save_npz  # noqa: E402
 
 
 def boxes_like(g, n, spread=0.25):
@@ -139,8 +141,8 @@ def case(K, seed):
     cot_e = torch.randn(320, 512, generator=g)
     (emb * cot_e).sum().backward()
     out.update(sine_pos=p.detach(), sine_embed=emb.detach(), sine_cot=cot_e, sine_grad=p.grad)
-    np.savez_compressed(os.path.join(OUT, f"clipops_C1_k{K}.npz"),
-                        **{k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()})
+    save_npz(os.path.join(OUT, f"clipops_C1_k{K}.npz"),
+             **{k: (v.detach().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in out.items()})
     print(f"clipops_C1_k{K}: cost {out['cost'].shape}, focal {per_layer.tolist()[:2]}, l1 {l1s.tolist()[:2]}")
 
 

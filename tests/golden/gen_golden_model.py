@@ -25,6 +25,8 @@ import torch.nn.functional as F
 
 REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(OUT))              # tests/: conftest.save_npz, fixtures split below 1 MiB a file
+from conftest import save_npz  # noqa: E402
 
 
 # --------------------------------------------------------------------------- stubs
@@ -106,7 +108,7 @@ def save(name, **arrs):
             out.update(v)
         else:
             out[k] = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-    np.savez_compressed(os.path.join(OUT, f"model_{name}.npz"), **out)
+    save_npz(os.path.join(OUT, f"model_{name}.npz"), **out)
     print(name, len(out), "arrays")
 
 

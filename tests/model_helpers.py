@@ -6,13 +6,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from conftest import GOLDEN_DIR
+from conftest import GOLDEN_DIR, load_npz
 from oracle import msda_oracle as oracle
 
 
 def load_model_golden(name):
-    with np.load(os.path.join(GOLDEN_DIR, f"model_{name}.npz")) as z:
-        return {k: z[k] for k in z.files}
+    return load_npz(os.path.join(GOLDEN_DIR, f"model_{name}.npz"))
 
 
 def state_from(g, prefix="w::"):

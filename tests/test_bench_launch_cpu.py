@@ -13,6 +13,8 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 def _run(args, **env):
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    # the ranks see no device on a machine with GPUs too: they all stop at the same check as on a host without one
+    e.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     e.update(env)
     return subprocess.run([sys.executable, BENCH] + args, env=e, capture_output=True, text=True, timeout=300)
 
@@ -63,3 +65,36 @@ def test_eight_rank_launch_rehearsal_rendezvous_thread_pools_and_one_json_line()
     want = max(1, int(cpu_quota() * 0.5 / 8))
     assert out["torch_threads"] == want and out["torch_threads_sum"] == 8.0 * want, out
     assert abs(out["cpu_quota_per_rank"] - cpu_quota() / 8) < 1e-9
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, r.stderr[-400:]
+
+
+_DUMP = """
+import sys
+root, dirs = sys.argv[1], sys.argv[2:]
+sys.path.insert(0, root)
+import torch
+import bench
+big = torch.arange(bench.DUMP_SAMPLE * 3 + 7, dtype=torch.float64)
+for out in dirs:
+    bench.dump_outputs(out, {"big": big, "small": torch.arange(5), "half": torch.ones(3, dtype=torch.bfloat16)})
+"""
+
+
+def test_dump_outputs_writes_floats_and_the_same_sample_every_time(tmp_path):
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    e = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _DUMP, ROOT] + dirs, env=e, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-800:]
+    a = {n: np.load(os.path.join(dirs[0], n + ".npy")) for n in ("big", "small", "half")}
+    b = {n: np.load(os.path.join(dirs[1], n + ".npy")) for n in ("big", "small", "half")}
+    assert a["big"].dtype == np.float64 and a["small"].dtype == np.float32 and a["half"].dtype == np.float32
+    assert np.array_equal(a["small"], np.arange(5, dtype=np.float32)) and np.array_equal(a["half"], np.ones(3))
+    assert 0 < a["big"].size < 3 * 2 ** 21 + 7          # a sample of the large array ...
+    assert np.all(np.diff(a["big"]) > 0) and a["big"][-1] < 3 * 2 ** 21 + 7   # ... of distinct elements, in order
+    for k in a:                                          # ... and the same one on every run
+        assert np.array_equal(a[k], b[k])

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import load_npz
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEVICES = ["cpu", pytest.param("cuda", marks=pytest.mark.gpu)]
 CASES = [1, 8]
@@ -19,8 +21,8 @@ CASES = [1, 8]
 def load(K, device):
     if device == "cuda" and not torch.cuda.is_available():
         pytest.skip("no GPU")
-    g = np.load(os.path.join(HERE, "golden", f"clipops_C1_k{K}.npz"))
-    return {k: torch.from_numpy(g[k]).to(device) for k in g.files}
+    g = load_npz(os.path.join(HERE, "golden", f"clipops_C1_k{K}.npz"))
+    return {k: torch.from_numpy(v).to(device) for k, v in g.items()}
 
 
 def close(got, want, rtol, atol, what=""):

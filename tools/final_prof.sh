@@ -10,7 +10,7 @@ cp profiles/traffic.json profiles/traffic_bwd.json /tmp/ 2>/dev/null
 # the bench reads profiles/traffic*.json: use the fresh ones for the lines below
 cp gpurun_out/profiles/traffic.json gpurun_out/profiles/traffic_bwd.json profiles/ 2>/dev/null
 bash tools/bench_lines.sh rest r06 > gpurun_out/r06_lines.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/lines/r06_bench_default_driver_cmd.err | tail -1 > gpurun_out/lines/r06_bench_default_driver_cmd.json
+bash tools/bench_lines.sh driver r06
 cut -c1-220 gpurun_out/lines/r06_bench_default_driver_cmd.json
 cat gpurun_out/r06_lines.log | tail -12
 ls gpurun_out/profiles
