@@ -1,5 +1,5 @@
-"""Build memotr_amd/lib/libmsda_hip.so (the operator) and libclip_ops_hip.so (fused small-tensor chains of the train
-step) with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
+step) and libframe_ops_hip.so (raw-frame resize / normalise) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -19,6 +19,9 @@ CLIP_SRC = os.path.join(_HERE, "csrc", "clip_ops.hip")
 CLIP_HDR = os.path.join(os.path.dirname(_HERE), "include", "clip_ops_hip.h")
 CLIP_LIB = os.path.join(LIB_DIR, "libclip_ops_hip.so")
 ASSIGN_CORE = os.path.join(_HERE, "csrc", "assign_core.h")
+FRAME_SRC = os.path.join(_HERE, "csrc", "frame_ops.hip")
+FRAME_HDR = os.path.join(os.path.dirname(_HERE), "include", "frame_ops_hip.h")
+FRAME_LIB = os.path.join(LIB_DIR, "libframe_ops_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -76,6 +79,13 @@ def build_clip_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(CLIP_SRC, CLIP_LIB, verbose)
 
 
+def build_frame_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(FRAME_LIB, (FRAME_SRC, FRAME_HDR)):
+        return FRAME_LIB
+    return _compile(FRAME_SRC, FRAME_LIB, verbose)
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
+    print(build_frame_lib(force=True, verbose=True))

@@ -10,6 +10,14 @@ One frame of lookahead (a recorded sequence always has it): ``tracker.step(image
 queues the backbone + encoder of the NEXT frame -- the half of a frame that does not depend on the tracks, ~3/4 of
 its kernel time -- on a side stream before the host blocks on this frame's scores, so the GPU works through it while
 the host does the track bookkeeping and issues the query updater (results are identical; tests/test_model_gpu.py).
+
+From decoded frames (uint8, H x W x 3, e.g. what ``cv2.imread`` returns) instead of normalised tensors:
+
+    for frame_idx, result in tracker.track(frames_u8, bgr=True):       # resize + normalise + pad on the GPU, lookahead
+        lines += tracker.mot_lines(frame_idx, result)
+
+``track`` is ``step_raw(frame, next_frame)`` in a loop: upload through pinned memory, one kernel (data/frames.py),
+then the same encode / decode path as ``step``.
 """
 from __future__ import annotations
 
@@ -17,6 +25,7 @@ from typing import List
 
 import torch
 
+from .data.frames import preprocess_frames, target_size
 from .models.runtime_tracker import RuntimeTracker
 from .models.utils import get_model
 from .structures.track_instances import TrackInstances
@@ -31,7 +40,7 @@ MOT_STYLE = ("DanceTrack", "SportsMOT", "MOT17", "MOT17_SPLIT")
 class SequenceTracker:
     def __init__(self, model, dataset_name: str = "DanceTrack", det_score_thresh: float = 0.7,
                  track_score_thresh: float = 0.6, result_score_thresh: float = 0.7, miss_tolerance: int = 5,
-                 use_dab: bool = True, area_thresh: int = 100):
+                 use_dab: bool = True, area_thresh: int = 100, raw_size=(800, 1536)):
         from .utils.host import respect_cpu_quota
         respect_cpu_quota()           # (a container's CFS quota vs torch's machine-sized thread pool: utils/host.py)
         self.model = model.eval()
@@ -49,6 +58,9 @@ class SequenceTracker:
         self._pending = None          # (image, encode result, event): the next frame's encode half, queued ahead
         self._slot = 0                # encode calls alternate between two graph slots (one may still be read)
         self._side = None
+        self.raw_size = raw_size      # step_raw: (short side, longest long side) of the resized frame; the reference's
+        self._staging = [None, None]  # step_raw: two pinned upload buffers, each with the event of its last copy
+        self._staging_i = 0
 
     @classmethod
     def from_config(cls, model, config: dict) -> "SequenceTracker":
@@ -134,6 +146,90 @@ class SequenceTracker:
             if torch.is_tensor(v) and v.is_cuda:
                 v.record_stream(main)
         self._pending = (image, enc, event)
+
+    # ------------------------------------------------------------------ raw uint8 frames
+    @torch.no_grad()
+    def step_raw(self, frame_u8, next_frame_u8=None, *, bgr: bool = False) -> TrackInstances:
+        """``step`` on a decoded frame: (H, W, 3) uint8, torch or numpy, RGB (``bgr=True``: cv2's order); ``ori_h`` and
+        ``ori_w`` are the frame's.  The frame is uploaded through a reusable pinned buffer with a non-blocking copy and
+        turned into the padded normalised batch by one kernel (data/frames.py), then takes the encode path of ``step``
+        (same slot alternation).  ``next_frame_u8``: the frame the next call will pass (the same object, unchanged until
+        then); its upload, kernel and encode half are queued on the side stream as ``_prefetch`` does for ``step``."""
+        ori_h, ori_w = int(frame_u8.shape[0]), int(frame_u8.shape[1])
+        pending, self._pending = self._pending, None
+        if pending is not None:
+            torch.cuda.current_stream(self.device).wait_event(pending[2])
+        enc = pending[1] if pending is not None and pending[0] is frame_u8 else self._encode_raw(frame_u8, bgr)
+        res = self.model(tracks=self.tracks, encoded=enc)
+        if next_frame_u8 is not None:
+            self._prefetch_raw(next_frame_u8, bgr)
+        previous, new = self.tracker.update(model_outputs=res, tracks=self.tracks)
+        self.tracks = self.core.postprocess_single_frame(previous, new, None)
+        return self._report(self.tracks[0], ori_h, ori_w)
+
+    def track(self, frames, *, bgr: bool = False):
+        """Generator over an iterable of uint8 frames: yields ``(frame_idx, result)``, one frame of lookahead."""
+        it = iter(frames)
+        done = object()
+        cur, idx = next(it, done), 0
+        while cur is not done:
+            nxt = next(it, done)
+            yield idx, self.step_raw(cur, None if nxt is done else nxt, bgr=bgr)
+            cur, idx = nxt, idx + 1
+
+    def _upload(self, frame_u8) -> torch.Tensor:
+        """The frame on the device, copied on the current stream.  Pageable host memory goes through one of two pinned
+        buffers (a copy from pageable memory blocks the host); a frame that is pinned already is copied as it is."""
+        frame = torch.from_numpy(frame_u8) if not torch.is_tensor(frame_u8) else frame_u8
+        if self.device.type != "cuda" or frame.device == self.device:
+            return frame
+        if frame.is_cuda:
+            return frame.to(self.device)
+        stream = torch.cuda.current_stream(self.device)
+        host, slot = frame, None
+        if not (frame.is_pinned() and frame.is_contiguous()):
+            slot, self._staging_i = self._staging_i, self._staging_i ^ 1
+            entry = self._staging[slot]
+            if entry is None or entry[0].shape != frame.shape:
+                entry = [torch.empty(frame.shape, dtype=torch.uint8, pin_memory=True), None]
+                self._staging[slot] = entry
+            elif entry[1] is not None:
+                entry[1].synchronize()          # the copy out of this buffer two uploads ago (long done)
+            host = entry[0]
+            host.copy_(frame)
+        dev = torch.empty(host.shape, dtype=torch.uint8, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        if slot is not None:
+            self._staging[slot][1] = stream.record_event()
+        return dev
+
+    def _encode_raw(self, frame_u8, bgr: bool, after=None) -> dict:
+        dev = self._upload(frame_u8)
+        if after is not None:                   # (the upload itself depends on nothing that stream has queued)
+            torch.cuda.current_stream(self.device).wait_stream(after)
+        frame = preprocess_frames(dev, bgr=bgr, size=target_size(dev.shape[0], dev.shape[1], *self.raw_size))
+        frame.encode_slot = self._slot
+        frame.encode_static_ok = True
+        self._slot ^= 1
+        return self.model(frame=frame, stage="encode")
+
+    def _prefetch_raw(self, frame_u8, bgr: bool) -> None:
+        if self.device.type != "cuda":
+            return
+        main = torch.cuda.current_stream(self.device)
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        side = self._side
+        with torch.cuda.stream(side):
+            # upload now, kernel and encode behind this frame's decode on main (it reads the OTHER slot)
+            enc = self._encode_raw(frame_u8, bgr, after=main)
+            event = side.record_event()
+        if torch.is_tensor(frame_u8) and frame_u8.is_cuda:
+            frame_u8.record_stream(side)
+        for v in enc.values():                  # produced on the side stream, consumed on main
+            if torch.is_tensor(v) and v.is_cuda:
+                v.record_stream(main)
+        self._pending = (frame_u8, enc, event)
 
     def mot_lines(self, frame_idx: int, tracks: TrackInstances) -> List[str]:
         if self.dataset_name not in MOT_STYLE:
