@@ -1,5 +1,6 @@
 """Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
-step) and libframe_ops_hip.so (raw-frame resize / normalise) with hipcc for gfx950 (cross-compiles without a GPU)."""
+step), libframe_ops_hip.so (raw-frame resize / normalise) and libaugment_ops_hip.so (training-clip augmentation) with
+hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -22,6 +23,9 @@ ASSIGN_CORE = os.path.join(_HERE, "csrc", "assign_core.h")
 FRAME_SRC = os.path.join(_HERE, "csrc", "frame_ops.hip")
 FRAME_HDR = os.path.join(os.path.dirname(_HERE), "include", "frame_ops_hip.h")
 FRAME_LIB = os.path.join(LIB_DIR, "libframe_ops_hip.so")
+AUGMENT_SRC = os.path.join(_HERE, "csrc", "augment_ops.hip")
+AUGMENT_HDR = os.path.join(os.path.dirname(_HERE), "include", "augment_ops_hip.h")
+AUGMENT_LIB = os.path.join(LIB_DIR, "libaugment_ops_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -85,7 +89,14 @@ def build_frame_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(FRAME_SRC, FRAME_LIB, verbose)
 
 
+def build_augment_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(AUGMENT_LIB, (AUGMENT_SRC, AUGMENT_HDR)):
+        return AUGMENT_LIB
+    return _compile(AUGMENT_SRC, AUGMENT_LIB, verbose)
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
     print(build_frame_lib(force=True, verbose=True))
+    print(build_augment_lib(force=True, verbose=True))

@@ -1,1 +1,3 @@
-"""Input side of the per-frame path: raw decoded frames to the padded normalised batch the model reads."""
+"""Input side: raw decoded frames to the padded normalised batch the model reads (frames.py, the per-frame path) and
+the training-clip augmentation (augment.py)."""
+from .augment import augment_clip, clip_batch  # noqa: F401
