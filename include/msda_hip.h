@@ -249,7 +249,8 @@ int msda_fused_backward_out_bf16(const uint16_t *value, const int64_t *shapes_de
  *                        the wide tensor once.  e >= M * D, e * sizeof(element) a multiple of 16; 0 or M * D: contiguous.
  *                        D = 32 float32 / bfloat16 calls only (the direct-gather forward, the row backward: the kernels the
  *                        decoder's calls take anyway); anything else returns MSDA_ENOTSUP and the caller passes a
- *                        contiguous copy.  The setting is consumed by that one call, successful or not. */
+ *                        contiguous copy.  The setting is consumed by that one call, successful or not: every entry
+ *                        point above reads and clears it before it looks at its arguments. */
 int msda_next_value_pixel_stride(long elements);
 
 /* ---- kernel selection (round 4, records reworked in round 5 = ABI 5, per-site poll = ABI 6; memotr_amd/csrc/msda_select.h) ----

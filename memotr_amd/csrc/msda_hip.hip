@@ -12,7 +12,8 @@
 //             logits, sampling locations from offsets + reference points, padding-mask fill of `value`
 // C ABI: include/msda_hip.h.  Design notes, byte counts and rooflines: DESIGN.md.
 //
-// Sources: this file holds the host side (options, kernel selection, launch planning, the C ABI); the kernels live
+// Sources: this file holds the host side's plans, the selector, the options and the C ABI; which kernels a call takes
+// is msda_dispatch_fwd.h / msda_dispatch_bwd.h (one function per path, the drivers at their ends); the kernels live
 // in msda_generic.h (any D / dtype), msda_fwd_gather.h (D = 32 through the vector L1), msda_fwd_win.h (pyramid
 // self-attention forward, LDS windows), msda_tile.h + msda_bwd_tile_lv.h / msda_bwd_bins.h (pyramid backward),
 // msda_bwd_rows.h (decoder-shaped backward), msda_fused_side.h (Jacobian side kernels), msda_select.h (statistics).
@@ -93,7 +94,7 @@ std::atomic<int> opt_fwd_grid_mult{32}, opt_bwd_grid_mult{16};
 std::atomic<int> opt_bwd_tile_margin{4};
 std::atomic<int> opt_bwd_split{1};        // fused backward with a workspace: prologue kernel + plain tiled kernel + finish kernel
 std::atomic<int> opt_bwd_wide_log2{12};   // tiled backward: row-magnitude range (log2) that makes a region "wide"; 0 = off
-std::atomic<int> opt_bwd_ablate{0};
+std::atomic<int> opt_bwd_ablate{0};       // profiling only: drop parts of the tiled backward (results are then wrong)
 std::atomic<int> opt_bwd_rows_block{0};   // threads per workgroup of msda_bwd_d32_rows (0: by problem size)
 std::atomic<int> opt_bwd_bins_strip{4};   // counting-sort backward: region rows per strip of the block -> region walk
 std::atomic<int> opt_bwd_bins_margin{6};     // small-margin level (level 0 of the selector)
@@ -129,7 +130,6 @@ std::atomic<int> opt_fwd_win_early{9};      // 0 / 2 / 4: level-0 points request
 constexpr int kWinEarlyW4 = 0;              // ... of the 128-register build (0 and 2 time the same; 0 needs 107 registers, no spill)
 std::atomic<int> opt_bwd_side_rows{1};      // slim split backward: side kernels with one lane per (query, head) row (0: one lane per point)
 std::atomic<int> opt_fwd_win_trace_lo{0}, opt_fwd_win_trace_hi{0};   // profiling: device address of the timeline buffer (31 + 31 bits)
-       // profiling only: drop parts of the tiled backward (results are then wrong)
 
 int fail(int code, const char *msg) {
     snprintf(g_err, sizeof(g_err), "%s", msg);
@@ -377,7 +377,8 @@ bool g_sel_pool_failed[64] = {false};
 unsigned long long g_sel_clock = 0, g_sel_tick = 0;
 thread_local unsigned long long g_site = 0;
 // msda_next_value_pixel_stride: elements between two pixels of `value` (and of `grad_value`) for the NEXT forward /
-// backward call of this thread (0: contiguous, M * D).  Read once -- by that call, whatever its outcome -- and cleared.
+// backward call of this thread (0: contiguous, M * D).  Every compute entry point takes (reads and clears) it as its first
+// statement and hands it down in the Call; nothing below the entry points reads it.
 thread_local long g_value_stride = 0;
 inline long take_value_stride() {
     const long v = g_value_stride;
@@ -599,648 +600,117 @@ int check_fused(const FusedArgs &fa, int M, int L, int P) {
     return MSDA_OK;
 }
 
-template <typename TV, typename TC>
-int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lstart, const TC *loc, const TC *attn,
-                 const FusedArgs &fa, int N, int S, int M, int D, int L, int Lq, int P, TV *out,
-                 const int64_t *shapes_host, hipStream_t stream) {
-    const long vstride = take_value_stride();
-    const bool fused = fa.proj != nullptr;
-    int rc = fused ? check_dims(value, shapes, lstart, fa.proj, fa.ref, out, N, S, M, D, L, Lq, P)
-                   : check_dims(value, shapes, lstart, loc, attn, out, N, S, M, D, L, Lq, P);
+// A side kernel of a call (zeroing, fused prologue / finish, the sort's stages): launched and checked under its own
+// name.  check_launch touches only the error text, so msda_last_kernel() keeps naming the call's main kernel.
+template <typename K, typename... A>
+int launch_side(const char *what, K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return check_launch(what);
+}
+
+constexpr int kNotTaken = 1 << 30;      // a path's answer when the call does not fit it: the driver tries the next one
+
+// One operator call: what the entry point was given (forward: `out`; backward: `grad_out` and the gradients) and the
+// facts every path asks about, computed once by finish_call.  The forward instantiates it with TG = TC.
+template <typename TV_, typename TC_, typename TG_>
+struct Call {
+    using TV = TV_; using TC = TC_; using TG = TG_;
+    // storage types the specialised (D = 32) kernels exist for
+    static constexpr bool kD32Type = sizeof(TC) == 4 && sizeof(TG) == 4 && (sizeof(TV) == 4 || sizeof(TV) == 2);
+    int N = 0, S = 0, M = 0, D = 0, L = 0, Lq = 0, P = 0;
+    const int64_t *shapes = nullptr, *lstart = nullptr, *shapes_host = nullptr;
+    const TC *loc = nullptr, *attn = nullptr;
+    FusedArgs fa;
+    const TV *value = nullptr;
+    TV *out = nullptr;
+    const TV *grad_out = nullptr, *fwd_out = nullptr;
+    TG *grad_value = nullptr;
+    TC *grad_loc = nullptr, *grad_attn = nullptr;
+    float *grad_proj = nullptr, *grad_ref_part = nullptr;
+    int zero_grad_value = 0;
+    float *workspace = nullptr;
+    size_t workspace_bytes = 0;
+    hipStream_t stream = nullptr;
+    long vstride = 0;           // msda_next_value_pixel_stride, taken by the entry point (0: contiguous); below: derived
+    bool fused = false, strided = false;
+    long value_elems = 0, value_bytes = 0, n_rows = 0;      // n_rows: (batch, query, head) rows
+    bool can32 = false;         // the specialised kernels can address this call
+    bool can_tile = false;      // backward: pyramid self-attention with host shapes (bins / tile_lv)
+
+    PointSrc src() const { return make_src(loc, attn, fa, M, L, P); }
+};
+
+// Validate a call and fill in its derived facts.  `io`: the forward's out / the backward's grad_out.  `empty`: no
+// queries -- nothing to compute (the stride of such a call is not looked at).
+template <typename C>
+int finish_call(C &c, const void *io, bool backward, bool &empty) {
+    using TV = typename C::TV;
+    c.fused = c.fa.proj != nullptr;
+    int rc = c.fused ? check_dims(c.value, c.shapes, c.lstart, c.fa.proj, c.fa.ref, io, c.N, c.S, c.M, c.D, c.L, c.Lq, c.P)
+                     : check_dims(c.value, c.shapes, c.lstart, c.loc, c.attn, io, c.N, c.S, c.M, c.D, c.L, c.Lq, c.P);
     if (rc) return rc;
-    if (fused && (rc = check_fused(fa, M, L, P))) return rc;
-    if ((long)N * Lq == 0) { g_err[0] = 0; return MSDA_OK; }
-    int variant = opt_fwd_variant.load();
-    constexpr bool kD32Type = sizeof(TC) == 4 && (sizeof(TV) == 4 || sizeof(TV) == 2);
-    // `value` as a slice of a wider tensor (msda_next_value_pixel_stride): the gather kernel only -- the call sites that
-    // use it are the decoder's (a few hundred queries), which take that kernel anyway
-    const bool strided = vstride != 0 && vstride != (long)M * D;
-    const long value_elems = strided ? (long)N * S * vstride : (long)N * S * M * D;
-    const long value_bytes = value_elems * (long)sizeof(TV);
-    const bool can32 = kD32Type && d32_ok(D, L, value_elems);
-    if (strided) {
-        if (vstride < (long)M * D || (vstride * (long)sizeof(TV)) % 16 != 0)
+    if (c.fused && (rc = check_fused(c.fa, c.M, c.L, c.P))) return rc;
+    if (backward && (!c.grad_value || (c.fused ? !c.grad_proj : (!c.grad_loc || !c.grad_attn))))
+        return fail(MSDA_EINVAL, "null gradient pointer");
+    const long row_elems = (long)c.M * c.D;
+    c.strided = c.vstride != 0 && c.vstride != row_elems;
+    if (backward && c.strided && c.zero_grad_value) return fail(MSDA_EINVAL, "value pixel stride: grad_value is the caller's to zero");
+    c.n_rows = (long)c.N * c.Lq * c.M;
+    empty = (long)c.N * c.Lq == 0;
+    if (empty) return MSDA_OK;
+    c.value_elems = (long)c.N * c.S * (c.strided ? c.vstride : row_elems);
+    c.value_bytes = c.value_elems * (long)sizeof(TV);
+    c.can32 = C::kD32Type && d32_ok(c.D, c.L, c.value_elems);
+    if (c.strided) {        // the gather forward and the rows backward only
+        if (c.vstride < row_elems || (c.vstride * (long)sizeof(TV)) % 16 != 0)
             return fail(MSDA_EINVAL, "value pixel stride: at least M * D elements, rows 16-byte aligned");
-        if (!can32) return fail(MSDA_ENOTSUP, "value pixel stride: D = 32 float32 / bfloat16 calls only");
-        variant = 3;
+        if (!backward && !c.can32) return fail(MSDA_ENOTSUP, "value pixel stride: D = 32 float32 / bfloat16 calls only");
+        if (backward && !(c.can32 && c.L * c.P <= kRowsMaxLP && c.n_rows < (1L << 31)))
+            return fail(MSDA_ENOTSUP, "value pixel stride: D = 32 float32 / bfloat16 calls of at most 64 points only");
     }
-    SelSlot *slot = nullptr;
-    int sel = 0;
-    bool sel_head_major = false;
-    if (variant == 0) {
-        // self-attention over the pyramid (one query per pixel): coarse levels from per-head LDS windows; every
-        // other D = 32 call: direct gather with 4 points (16 rows) in flight -- best of the sweeps in profiles/
-        // (bf16 rows, round 6: the same kernel on 64-byte rows exists -- "fwd_win_bf16" 1 or "fwd_variant" 12 -- and is
-        //  slower than the gather kernel: halving the LDS bytes bought nothing, the widening costs VALU)
-        const bool pyramid = can32 && (sizeof(TV) == 4 || opt_fwd_win_bf16.load() != 0) && shapes_host != nullptr && Lq == S &&
-                             L <= kWinMaxL && L * P <= 16 && opt_fwd_win_auto.load() != 0;
-        variant = pyramid ? 12 : (can32 ? 3 : 1);
-        if (pyramid) {      // msda_select.h: windows while the points stay near their queries, else the head-major gather
-            slot = sel_acquire(0, M, L, P, (int)sizeof(TV), stream);
-            bool probe = false;
-            sel = sel_level(slot, 0, probe, slot != nullptr && stream_capturing(stream));
-            // "deterministic": the windowed and the gather kernel add a row's points in different orders (same values to
-            // 2e-5, different last bits), and the selector moves a call site between them from statistics of EARLIER calls;
-            // with the option on, identical calls return identical bits -- the windowed kernel's, whose results do not depend
-            // on where its windows sit (the record keeps measuring, nothing follows it)
-            if (opt_deterministic.load()) sel = 0;
-            if (sel >= 1) { variant = 3; sel_head_major = true; }
-        }
-    } else if (variant == 12 && can32 && shapes_host != nullptr) {
-        slot = sel_acquire(0, M, L, P, (int)sizeof(TV), stream);     // forced: the selector only measures
-        bool probe = false;
-        (void)sel_level(slot, 0, probe, slot != nullptr && stream_capturing(stream));
-        sel = 0;
-    }
-    if (variant >= 2 && !can32) variant = 1;
-    if (variant == 1) {
-        const long total = (long)N * Lq * M * D;
-        const int grid = clamp_grid((total + 255) / 256, 32);
-        if constexpr (sizeof(TC) == 4) {
-            const PointSrc src = make_src(loc, attn, fa, M, L, P);
-            if (fused) {
-                g_kernel = "msda_fwd_generic<fused>";
-                hipLaunchKernelGGL((msda_fwd_generic<TV, TC, true>), dim3(grid), dim3(256), 0, stream, value, shapes,
-                                   lstart, (const TC *)nullptr, (const TC *)nullptr, src, N, S, M, D, L, Lq, P, out);
-                return check_launch(g_kernel);
-            }
-        }
-        g_kernel = "msda_fwd_generic";
-        hipLaunchKernelGGL((msda_fwd_generic<TV, TC, false>), dim3(grid), dim3(256), 0, stream, value, shapes, lstart,
-                           loc, attn, PointSrc{}, N, S, M, D, L, Lq, P, out);
-        return check_launch(g_kernel);
-    }
-    if constexpr (kD32Type) {
-        const PointSrc src = make_src(loc, attn, fa, M, L, P);
-        {
-            if (variant == 12) {
-                WinPlan wp;
-                size_t lds = 0;
-                const int mgs = opt_fwd_win_margins.load();
-                const int margins[kWinMaxL] = {mgs & 15, (mgs >> 4) & 15, (mgs >> 8) & 15, (mgs >> 12) & 15};
-                // Region shape and workgroup size (0 = auto).  Round 5: 16 x 16-pixel regions and 512 threads -- 340 rows
-                // share one set of windows and one prologue (8 x 8: 85), two workgroups = 16 wavefronts per CU at 128
-                // registers; border regions hold only the rows that exist and are walked last, so the 616 workgroups
-                // of one 800 x 1333 image end together on the 512 slots (46.0 vs 55.1 us fused, N = 5: 224 vs 289 us;
-                // profiles/r05_fwd_win_sweep_*.txt).  A geometry that shape cannot take falls back to 8 x 8 / 256.
-                int threads = opt_fwd_win_block.load();
-                int rlogy = opt_fwd_win_rlog.load(), rlogx = opt_fwd_win_rlogx.load();
-                const bool auto_shape = threads == 0 && rlogy == 0 && rlogx == 0;
-                if (threads != 512 && threads != 384 && threads != 128 && threads != 256) threads = auto_shape ? 512 : 256;
-                if (rlogy == 0) rlogy = auto_shape ? 4 : 3;
-                if (rlogx == 0) rlogx = rlogy;
-                constexpr int kMaskGroups = sizeof(TV) == 4 ? 8 : 4;      // fill groups a wavefront's lanes cover per level
-                bool planned = make_win_plan(wp, shapes_host, N, S, M, D, L, Lq, P, value_bytes, rlogx, rlogy,
-                                             opt_fwd_win_l0.load(), margins, threads, lds, (int)sizeof(TV)) &&
-                               !(src.mask != nullptr && wp.wgroups_max > kMaskGroups * (threads / 64));
-                // Equal regions of any size (make_win_plan_grid) where they fill the workgroup slots in fewer rounds than
-                // the power-of-two ones: asked for by size ("fwd_win_rsy" / "fwd_win_rsx"), or chosen by estimate for the
-                // default shape (win_grid_choice, cached per geometry)
-                {
-                    int rsy = opt_fwd_win_rsy.load(), rsx = opt_fwd_win_rsx.load();
-                    if (rsy <= 0 && rsx <= 0 && auto_shape && planned && opt_fwd_win_grid.load() != 0 && sizeof(TV) == 4)
-                        win_grid_choice(wp, shapes_host, N, S, M, D, L, Lq, P, value_bytes, opt_fwd_win_l0.load(), margins,
-                                        threads, mgs, rsy, rsx);
-                    if (rsy > 0 || rsx > 0) {
-                        if (rsy <= 0) rsy = rsx;
-                        if (rsx <= 0) rsx = rsy;
-                        WinPlan gp_;
-                        size_t glds = 0;
-                        if (make_win_plan_grid(gp_, shapes_host, N, S, M, D, L, Lq, P, value_bytes, rsy, rsx,
-                                               opt_fwd_win_l0.load(), margins, threads, glds, (int)sizeof(TV)) &&
-                            !(src.mask != nullptr && gp_.wgroups_max > kMaskGroups * (threads / 64))) {
-                            wp = gp_;
-                            lds = glds;
-                            planned = true;
-                        }
-                    }
-                }
-                if (!planned && auto_shape) {
-                    threads = 256;
-                    planned = make_win_plan(wp, shapes_host, N, S, M, D, L, Lq, P, value_bytes, 3, 3,
-                                            opt_fwd_win_l0.load(), margins, threads, lds, (int)sizeof(TV)) &&
-                              !(src.mask != nullptr && wp.wgroups_max > kMaskGroups * (threads / 64));
-                }
-                // (bf16 rows: the default shape only -- 512 threads, no early loads, no profiling build; else the gather)
-                if (sizeof(TV) == 2 && (threads != 512 || opt_fwd_win_ablate.load() != 0 || opt_fwd_win_trace_lo.load() != 0 ||
-                                        opt_fwd_win_trace_hi.load() != 0))
-                    planned = false;
-                if (planned) {
-                    const int grid = (wp.n_blocks + 7) & ~7;
-#define MSDA_LAUNCH_WIN(FU, WPS, NE, NAME)                                                                           \
-    do {                                                                                                             \
-        rc = allow_big_lds(msda_fwd_d32_win<TV, FU, WPS, NE>, lds);                                                  \
-        if (rc) return rc;                                                                                           \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_fwd_d32_win<TV, FU, WPS, NE>), dim3(grid), dim3(threads), lds, stream,              \
-                           value, lstart, src, out, wp);                                                             \
-    } while (0)
-#define MSDA_LAUNCH_WIN_T(FU, WPS, NE, NAME)                                                                         \
-    do {                                                                                                             \
-        rc = allow_big_lds(msda_fwd_d32_win<TV, FU, WPS, NE, true>, lds);                                            \
-        if (rc) return rc;                                                                                           \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_fwd_d32_win<TV, FU, WPS, NE, true>), dim3(grid), dim3(threads), lds, stream,        \
-                           value, lstart, src, out, wp);                                                             \
-    } while (0)
-#define MSDA_LAUNCH_WIN_P(FU, WPS, NE, PB, NAME)                                                                     \
-    do {                                                                                                             \
-        rc = allow_big_lds(msda_fwd_d32_win<TV, FU, WPS, NE, false, PB>, lds);                                       \
-        if (rc) return rc;                                                                                           \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_fwd_d32_win<TV, FU, WPS, NE, false, PB>), dim3(grid), dim3(threads), lds, stream,   \
-                           value, lstart, src, out, wp);                                                             \
-    } while (0)
-                    wp.ablate = opt_fwd_win_ablate.load();
-                    wp.trace = reinterpret_cast<unsigned long long *>(((unsigned long long)opt_fwd_win_trace_hi.load() << 31) |
-                                                                      (unsigned long long)opt_fwd_win_trace_lo.load());
-                    // The kernel's publisher is wavefront 1: a 64-thread workgroup (options only) runs without statistics.
-                    // (The share's denominator counts a wavefront's staged rows sixteen steps per ballot, any step count.)
-                    const int win_nw = threads / 64;
-                    const bool stats_ok = slot != nullptr && win_nw >= 2;
-                    if (stats_ok) {     // (cumulative counters, fixed addresses: a captured launch counts like an eager one)
-                        wp.stats = slot->dev;
-                        wp.stats_host = slot->host_dev;
-                        wp.sel_level = sel;
-                    }
-                    // windows placed from the record's running mean offsets (no round trip in front of the fill); without
-                    // a record, or on request, every workgroup measures its own first ("fwd_win_place" 1)
-                    wp.measure = (!stats_ok || M > kSelHintHeads || L > kSelHintLevels || opt_fwd_win_place.load() != 0) ? 1 : 0;
-                    // register budget by what the workgroup shape admits: three 256-thread workgroups per CU (40-53 KB
-                    // of LDS each) -> 168 registers, all four level-0 points requested before the LDS phase; 512-thread
-                    // workgroups (two per CU) or four small ones -> 128 registers, two of them
-                    int wps = opt_fwd_win_wps.load();
-                    const bool wide = wps == 2 && threads <= 256 && sizeof(TV) == 4 && !wp.trace && !wp.ablate;
-                    if (wps != 3 && wps != 4) wps = (threads <= 256 && lds + 640 > 40 * 1024) ? 3 : 4;
-                    int early = opt_fwd_win_early.load();          // 0 / 2 / 4 points; anything else: by budget
-                    if (threads > 256) {
-                        wps = 4;
-                        if (early == 4) early = 2;
-                    }
-                    if (early != 0 && early != 2 && early != 4) early = wps == 3 ? 4 : kWinEarlyW4;
-                    if (early == 4) wps = 3;
-                    // (the profiling instantiation -- timeline stamps, ablation bits -- exists for the default shape only)
-                    if ((wp.trace || wp.ablate) && (wps == 3 || early == 2))
-                        return fail(MSDA_EINVAL, "fwd_win_trace / fwd_win_ablate: profiling build of the default launch shape only");
-                    if constexpr (sizeof(TV) == 4) {
-                        if (wide) {     // "fwd_win_wps" 2: two wavefronts per SIMD, 256 registers, twelve LDS points per wait
-                            // (six points per wait, "p6", was built and measured too: 67.5 / 70.1 us against p12's 65.9 / 68.6
-                            //  -- profiles/r06_fwd_win_sweep_wide.txt; not kept in the library)
-                            const int e4 = opt_fwd_win_early.load() == 4;
-                            if (fused) {
-                                if (e4) MSDA_LAUNCH_WIN_P(true, 2, 4, 12, "msda_fwd_d32_win<fused,w2,e4,p12>");
-                                else MSDA_LAUNCH_WIN_P(true, 2, 0, 12, "msda_fwd_d32_win<fused,w2,p12>");
-                            } else {
-                                if (e4) MSDA_LAUNCH_WIN_P(false, 2, 4, 12, "msda_fwd_d32_win<w2,e4,p12>");
-                                else MSDA_LAUNCH_WIN_P(false, 2, 0, 12, "msda_fwd_d32_win<w2,p12>");
-                            }
-                            return check_launch(g_kernel);
-                        }
-                    }
-                    if constexpr (sizeof(TV) == 2) {       // bf16 rows: the default shape only (512 threads, no early loads)
-                        if (fused) MSDA_LAUNCH_WIN(true, 4, 0, "msda_fwd_d32_win<bf16,fused,w4>");
-                        else MSDA_LAUNCH_WIN(false, 4, 0, "msda_fwd_d32_win<bf16,w4>");
-                    } else {
-                    if (wps == 3) {
-                            if (fused) MSDA_LAUNCH_WIN(true, 3, 4, "msda_fwd_d32_win<fused,w3,e4>");
-                            else MSDA_LAUNCH_WIN(false, 3, 4, "msda_fwd_d32_win<w3,e4>");
-                        } else if (early == 2) {
-                            if (fused) MSDA_LAUNCH_WIN(true, 4, 2, "msda_fwd_d32_win<fused,w4,e2>");
-                            else MSDA_LAUNCH_WIN(false, 4, 2, "msda_fwd_d32_win<w4,e2>");
-                        } else {
-                            if (fused) {
-                                if (wp.trace || wp.ablate) MSDA_LAUNCH_WIN_T(true, 4, 0, "msda_fwd_d32_win<fused,w4>");
-                                else MSDA_LAUNCH_WIN(true, 4, 0, "msda_fwd_d32_win<fused,w4>");
-                            } else {
-                                if (wp.trace || wp.ablate) MSDA_LAUNCH_WIN_T(false, 4, 0, "msda_fwd_d32_win<w4>");
-                                else MSDA_LAUNCH_WIN(false, 4, 0, "msda_fwd_d32_win<w4>");
-                            }
-                        }
-                    }
-#undef MSDA_LAUNCH_WIN
-#undef MSDA_LAUNCH_WIN_P
-#undef MSDA_LAUNCH_WIN_T
-                    return check_launch(g_kernel);
-                }
-                variant = 3;  // the windowed kernel does not apply to this call
-            }
-        }
-        if (variant > 4) variant = 3;
-        constexpr int ROWS = RowGeom<TV>::kRows;
-        int block = opt_fwd_block.load();
-        if (block < 64 || block > 256 || (block & 63)) block = 256;  // kernels carry __launch_bounds__(256)
-        const int wpb = block / 64;
-        const int head_major = (opt_fwd_head_major.load() != 0 || sel_head_major) && (long)N * Lq >= 4096 ? 1 : 0;
-        const long n_tasks = head_major ? (((long)N * Lq + ROWS - 1) / ROWS) * M : ((long)N * Lq * M + ROWS - 1) / ROWS;
-        // small problems: one wave per block so every task gets its own CU slot
-        int use_block = block;
-        if (n_tasks < (long)kNumCU * wpb) use_block = 64;
-        const int uwpb = use_block / 64;
-        int grid = clamp_grid((n_tasks + uwpb - 1) / uwpb, opt_fwd_grid_mult.load());
-        grid = (grid + 7) & ~7;  // whole blocks per XCD residue
-        const size_t lds = (size_t)uwpb * ROWS * (2 * L * P + 1) * 16;
-#define MSDA_LAUNCH_FWD(PTS, FU, NAME)                                                                               \
-    do {                                                                                                             \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_fwd_d32_gather<PTS, TV, FU>), dim3(grid), dim3(use_block), lds, stream, value,      \
-                           shapes, lstart, src, N, S, M, L, Lq, P, out, (unsigned)value_bytes, head_major,          \
-                           (unsigned)((strided ? vstride : (long)M * D) * (long)sizeof(TV)));                         \
-    } while (0)
-        // (four points = 16 corner rows in flight per lane: the best of the round-1 sweep, profiles/r01_kbench_fwd_sweep.txt;
-        //  the 1- and 2-point instantiations went in round 5 -- variants 2, 3, 4 all mean this kernel)
-        if (fused) MSDA_LAUNCH_FWD(4, true, sizeof(TV) == 2 ? "msda_fwd_d32_gather<4,bf16,fused>" : "msda_fwd_d32_gather<4,fused>");
-        else MSDA_LAUNCH_FWD(4, false, sizeof(TV) == 2 ? "msda_fwd_d32_gather<4,bf16>" : "msda_fwd_d32_gather<4>");
-#undef MSDA_LAUNCH_FWD
-        return check_launch(g_kernel);
-    }
-    return fail(MSDA_ENOTSUP, "no specialised forward for this dtype");
+    c.can_tile = !c.strided && c.can32 && c.shapes_host && c.Lq == c.S && c.L <= kTileMaxL && c.grad_ref_part == nullptr;
+    return MSDA_OK;
+}
+
+#include "msda_dispatch_fwd.h"
+#include "msda_dispatch_bwd.h"
+
+// ---- the entry points' bodies: the C types of the ABI cast to the kernels' (uint16_t -> bf16_t), the arguments into a
+//      Call.  `vstride` is what the entry point took from msda_next_value_pixel_stride ----
+template <typename TV, typename TC>
+int run_forward(long vstride, const void *value, const int64_t *shapes, const int64_t *lstart, const TC *loc, const TC *attn,
+                const FusedArgs &fa, int N, int S, int M, int D, int L, int Lq, int P, void *out, const int64_t *shapes_host,
+                void *stream) {
+    Call<TV, TC, TC> c;
+    c.N = N; c.S = S; c.M = M; c.D = D; c.L = L; c.Lq = Lq; c.P = P;
+    c.shapes = shapes; c.lstart = lstart; c.shapes_host = shapes_host;
+    c.loc = loc; c.attn = attn; c.fa = fa;
+    c.value = (const TV *)value; c.out = (TV *)out;
+    c.stream = (hipStream_t)stream; c.vstride = vstride;
+    return forward_impl(c);
 }
 
 template <typename TV, typename TC, typename TG>
-int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lstart, const TC *loc, const TC *attn,
-                  const FusedArgs &fa, const TV *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                  TG *grad_value, TC *grad_loc, TC *grad_attn, float *grad_proj, float *grad_ref_part,
-                  int zero_grad_value, const int64_t *shapes_host, hipStream_t stream, float *workspace = nullptr,
-                  size_t workspace_bytes = 0, const TV *fwd_out = nullptr) {
-    const long vstride = take_value_stride();
-    const bool fused = fa.proj != nullptr;
-    // `fwd_out` (round 6): the forward's output of the same call, when the caller still holds it.  sum_j a_j ga_j of the
-    // softmax Jacobian IS <grad_out_row, out_row>, so with it the counting-sort backward needs no side kernel
-    const bool soft_ok = fused && fwd_out != nullptr && sizeof(TV) == 4 && L * P == 16 && fa.ref_dim == 2 &&
-                         (fa.proj_stride % 4) == 0 && ((2 * M * L * P) % 4) == 0 && (((uintptr_t)fa.proj) & 15) == 0 &&
-                         L == 4 && P == 4 && grad_ref_part == nullptr && opt_bwd_soft.load() != 0;
-    int rc = fused ? check_dims(value, shapes, lstart, fa.proj, fa.ref, grad_out, N, S, M, D, L, Lq, P)
-                   : check_dims(value, shapes, lstart, loc, attn, grad_out, N, S, M, D, L, Lq, P);
-    if (rc) return rc;
-    if (fused) {
-        if ((rc = check_fused(fa, M, L, P))) return rc;
-        if (!grad_value || !grad_proj) return fail(MSDA_EINVAL, "null gradient pointer");
-    } else if (!grad_value || !grad_loc || !grad_attn) {
-        return fail(MSDA_EINVAL, "null gradient pointer");
-    }
-    // grad_value is accumulated into: zeroed here on request -- by a kernel, not a memset node (a replayed hipGraph of
-    // ROCm 7.2 does not order MEMSET nodes behind the kernels before them unless DEBUG_CLR_GRAPH_PACKET_CAPTURE=0,
-    // tools/graph_memset_probe.py) -- together with whatever else the chosen path wants cleared (the sorted backward's
-    // bucket totals: one launch instead of two)
-    const size_t gv_words = (size_t)N * S * M * D * (sizeof(TG) / 4);
-    auto zero_launch = [&](unsigned *extra, unsigned extra_n) -> int {
-        if (!zero_grad_value && extra_n == 0u) return MSDA_OK;
-        const size_t n1 = zero_grad_value ? gv_words : 0;
-        const size_t blocks = (n1 / 4 + extra_n + 255) / 256;
-        hipLaunchKernelGGL(msda_zero_words_kernel, dim3((unsigned)(blocks < 2048 ? (blocks ? blocks : 1) : 2048)), dim3(256), 0, stream,
-                           reinterpret_cast<unsigned *>(grad_value), n1, extra, extra_n);
-        return check_launch("msda_zero_words_kernel");
-    };
-    // `value` and `grad_value` as slices of wider tensors (msda_next_value_pixel_stride): the rows kernel only, and the
-    // caller owns the zeroing of the whole gradient tensor
-    const bool strided = vstride != 0 && vstride != (long)M * D;
-    if (strided && zero_grad_value) return fail(MSDA_EINVAL, "value pixel stride: grad_value is the caller's to zero");
-    if ((long)N * Lq == 0) return zero_launch(nullptr, 0u);
-    int variant = opt_bwd_variant.load();
-    const long value_elems = strided ? (long)N * S * vstride : (long)N * S * M * D;
-    const long value_bytes = value_elems * (long)sizeof(TV);
-    constexpr bool kD32Type = sizeof(TC) == 4 && sizeof(TG) == 4 && (sizeof(TV) == 4 || sizeof(TV) == 2);
-    if (strided) {
-        if (vstride < (long)M * D || (vstride * (long)sizeof(TV)) % 16 != 0)
-            return fail(MSDA_EINVAL, "value pixel stride: at least M * D elements, rows 16-byte aligned");
-        if (!(kD32Type && d32_ok(D, L, value_elems) && L * P <= kRowsMaxLP && (long)N * Lq * M < (1L << 31)))
-            return fail(MSDA_ENOTSUP, "value pixel stride: D = 32 float32 / bfloat16 calls of at most 64 points only");
-        variant = 3;        // (any value the pyramid / sorted branches do not claim: straight to the rows kernel)
-    }
-    const bool can_tile = !strided && kD32Type && d32_ok(D, L, value_elems) && shapes_host && Lq == S && L <= kTileMaxL &&
-                          grad_ref_part == nullptr;
-    // Measured on MI355X (profiles/): per-contribution global float atomics cap the backward at ~1.1 ms
-    // for the encoder call (L2 atomic throughput; the row-per-block kernel's 32-consecutive-lane pattern
-    // is the fastest of them).  Self-attention over the pyramid (Lq == S, host shapes known) therefore
-    // takes the region-tiled kernel that pre-reduces grad_value in fixed-point LDS windows; every other call
-    // (decoder queries) takes the row-per-block kernel.
-    // Self-attention over the pyramid: the counting-sort kernel (msda_bwd_bins.h, round 4: 145 us at the encoder
-    // shape; tile_lv 218, tile_q2 317), at the window margin the measured off-window share asks for -- or, when most
-    // points leave even the large window (uniformly random locations), no windows at all (msda_select.h).
-    SelSlot *slot = nullptr;
-    int sel = 0, bins_margin = opt_bwd_bins_margin.load(), bins_shrink = 0;
-    if (kD32Type && can_tile && (variant == 0 || variant == 12)) {
-        slot = sel_acquire(1, M, L, P, (int)sizeof(TV), stream);
-        bool probe = false;
-        sel = sel_level(slot, 1, probe, slot != nullptr && stream_capturing(stream));
-        if (variant == 12) sel = opt_sel_level.load() >= 0 ? sel : 0;         // forced: the selector only measures
-        if (sel >= 1) {
-            bins_shrink = opt_bwd_bins_margin_hi.load() - bins_margin;
-            bins_margin = opt_bwd_bins_margin_hi.load();
-            if (bins_shrink < 0) bins_shrink = 0;
-        }
-        if (variant == 0) variant = sel >= 2 ? (opt_bwd_sorted.load() ? 13 : 1) : 12;
-    }
-    // ---- variant 13: grad_value by sort + gather through the caller's scratch (msda_bwd_sorted.h); everything else of
-    //      the call from msda_bwd_d32_rows without its atomics.  Not tied to the pyramid: any D = 32 call the rows kernel
-    //      takes.  Too little scratch (or none): the rows kernel with its atomics, below ----
-    if constexpr (kD32Type) {
-        if (variant == 13) {
-            const long n_rows13 = (long)N * Lq * M;
-            const size_t fused_bytes = fused ? (((size_t)n_rows13 * L * P * 3 * sizeof(float) + 255) & ~(size_t)255) : 0;
-            SortPlan sp;
-            const bool fits = d32_ok(D, L, value_elems) && L * P <= kRowsMaxLP && n_rows13 < (1L << 31) &&
-                              workspace != nullptr && workspace_bytes > fused_bytes &&
-                              make_sort_plan(sp, N, S, M, L, Lq, P, sizeof(TV), (unsigned char *)workspace + fused_bytes,
-                                             opt_bwd_sort_qc.load(), opt_bwd_sort_emult.load()) &&
-                              fused_bytes + sp.bytes <= workspace_bytes &&
-                              sort_dots_lds(sp.qc, L * P, sp.nbk).bytes <= 64u * 1024u;
-            if (fits) {
-                // grad_value (on request) and the bucket totals start from zero: one launch
-                if ((rc = zero_launch(sp.cursor, (unsigned)((size_t)N * M * sp.nbk)))) return rc;
-                const PointSrc src = make_src(loc, attn, fa, M, L, P);
-                const int threads = 256, per = threads / 32;
-                const int rgrid = clamp_grid((n_rows13 + per - 1) / per, 64);
-                const unsigned gv_bytes = (unsigned)(value_elems * 4);
-                const unsigned n_cursor = (unsigned)((size_t)N * M * sp.nbk);
-                const bool b16 = sizeof(TV) == 2;
-                // 1. fused: the softmax weights once per row into the scratch; the locations too unless the kernels below
-                //    can compute them from the raw projection themselves (the slim form of the split backward: L * P = 16,
-                //    16-byte aligned rows -- one lane per row in both side kernels)
-                PointSrc src_k = src;
-                int fused_loc = 0, offsets_done = 0, soft16 = 0;
-                bool slim = false;
-                if (fused) {
-                    float *loc_ws = workspace, *attn_ws = workspace + (size_t)n_rows13 * L * P * 2;
-                    slim = L * P == 16 && (fa.proj_stride % 4) == 0 && (src.n_off % 4) == 0 && grad_ref_part == nullptr &&
-                           (((uintptr_t)fa.proj | (uintptr_t)grad_proj | (uintptr_t)workspace) & 15) == 0 &&
-                           opt_bwd_side_rows.load() != 0;
-                    if (slim) {
-                        // L * P = 16, 2-d reference points (the encoder's): the sixteen lanes of a row compute its softmax
-                        // in the dots and emit kernels themselves (one function, the bits of msda_fused_attn16_rows_kernel)
-                        // and the dots kernel applies the softmax Jacobian -- no side kernel, no weights in HBM.  4-d
-                        // reference points keep the weights in the scratch for the finishing kernel's location Jacobian
-                        fused_loc = 1;
-                        offsets_done = fa.ref_dim == 2 ? 1 : 0;
-                        soft16 = offsets_done;
-                        if (!soft16)
-                            hipLaunchKernelGGL(msda_fused_attn16_rows_kernel, dim3(clamp_grid((n_rows13 + 255) / 256, 32)),
-                                               dim3(256), 0, stream, src, (unsigned)n_rows13, (unsigned)M, attn_ws);
-                    } else if (L * P <= 16) {
-                        hipLaunchKernelGGL(msda_fused_points16_kernel, dim3(clamp_grid((n_rows13 * 16 + 255) / 256, 32)),
-                                           dim3(256), 0, stream, shapes, src, n_rows13, M, L, P, loc_ws, attn_ws);
-                    } else {
-                        hipLaunchKernelGGL(msda_fused_points_kernel, dim3(clamp_grid((n_rows13 * 8 + 255) / 256, 16)),
-                                           dim3(256), 0, stream, shapes, src, n_rows13, M, L, P, loc_ws, attn_ws);
-                    }
-                    if ((rc = check_launch("msda_fused_points_kernel"))) return rc;
-                    src_k.loc = loc_ws;
-                    src_k.attn = attn_ws;
-                }
-                const unsigned go_bytes = (unsigned)((size_t)n_rows13 * 32 * sizeof(TV));
-                // 2. the bucket totals start from zero; then, per (batch, head, chunk of queries): grad_loc / grad_attn
-                //    (fused: the columns of grad_proj) and the chunk's corner histogram
-                const SortDotsLds dl = sort_dots_lds(sp.qc, L * P, sp.nbk);
-                const int pgrid = (N * M * sp.nchunk + 7) & ~7;
-                // (with gradients of the reference points wanted -- no caller of this package asks for them on this path --
-                //  the rows kernel without its atomics runs AFTER and overwrites the columns of grad_proj with its own,
-                //  finished, results next to grad_ref_part; the dots kernel then only counts)
-                hipLaunchKernelGGL((msda_bwd_sort_dots<TV>), dim3(pgrid), dim3(kSortThreads), dl.bytes, stream, value, shapes,
-                                   lstart, src_k, fused_loc, offsets_done, soft16, grad_out, (float *)grad_loc, (float *)grad_attn,
-                                   fused ? grad_proj : (float *)nullptr, sp, dl, (unsigned)value_bytes);
-                if ((rc = check_launch("msda_bwd_sort_dots"))) return rc;
-                if (fused && grad_ref_part != nullptr) {
-                    hipLaunchKernelGGL((msda_bwd_d32_rows<TV, true, false>), dim3(rgrid), dim3(threads), 0, stream, value, shapes,
-                                       lstart, src, grad_out, N, S, M, L, Lq, P, (float *)grad_value, (float *)nullptr,
-                                       (float *)nullptr, grad_proj, grad_ref_part, (unsigned)value_bytes, gv_bytes,
-                                       (unsigned *)nullptr, 0u);
-                    if ((rc = check_launch("msda_bwd_d32_rows<no atomics>"))) return rc;
-                } else if (fused && !soft16) {       // (soft16: finished by the dots kernel)
-                    if (L * P <= 16)
-                        hipLaunchKernelGGL(msda_fused_finish16_kernel, dim3(clamp_grid((n_rows13 * 16 + 255) / 256, 32)),
-                                           dim3(256), 0, stream, shapes, src_k, n_rows13, M, L, P, grad_proj, offsets_done);
-                    else
-                        hipLaunchKernelGGL(msda_fused_finish_kernel, dim3(clamp_grid((n_rows13 * 8 + 255) / 256, 16)),
-                                           dim3(256), 0, stream, shapes, src_k, n_rows13, M, L, P, grad_proj);
-                    if ((rc = check_launch("msda_fused_finish_kernel"))) return rc;
-                }
-                // 3. scan -> emit -> gather
-                const size_t hist_lds = (size_t)sp.nbk * 4;
-                const int egrid = (N * M * ((sp.nchunk + sp.emult - 1) / sp.emult) + 7) & ~7;
-                hipLaunchKernelGGL(msda_bwd_sort_scan, dim3(N * M), dim3(kSortThreads), 0, stream, sp);
-                hipLaunchKernelGGL(msda_bwd_sort_emit, dim3(egrid), dim3(kSortThreads), hist_lds, stream, shapes, lstart, src_k,
-                                   fused_loc, soft16, sp);
-                if ((rc = check_launch("msda_bwd_sort_emit"))) return rc;
-                const int ggrid = (N * M * sp.max_items + 7) & ~7;
-                const size_t glds = (size_t)(kSortSlice + 2) * 8 + (size_t)kSortBP * 8;
-                g_kernel = fused ? (b16 ? "msda_bwd_d32_sorted<bf16,fused>" : "msda_bwd_d32_sorted<fused>")
-                                 : (b16 ? "msda_bwd_d32_sorted<bf16>" : "msda_bwd_d32_sorted");
-                hipLaunchKernelGGL((msda_bwd_sort_gather<TV>), dim3(ggrid), dim3(kSortThreads), glds, stream, grad_out,
-                                   (float *)grad_value, sp, go_bytes);
-                if ((rc = check_launch(g_kernel))) return rc;
-                hipLaunchKernelGGL(msda_bwd_sort_reduce, dim3((N * M * sp.nbk + 7) & ~7), dim3(kSortThreads), 0, stream,
-                                   (float *)grad_value, sp);
-                {
-                    const char *name = g_kernel;
-                    rc = check_launch("msda_bwd_sort_reduce");
-                    g_kernel = name;
-                }
-                return rc;
-            }
-            variant = 1;        // (-> msda_bwd_d32_rows with its atomics, below)
-        }
-    }
-    if (variant == 13) variant = 1;
-    if ((rc = zero_launch(nullptr, 0u))) return rc;
-    if (variant == 0 || (variant >= 2 && variant != 10 && variant != 12)) variant = can_tile && P <= 8 ? 10 : 1;
-    if (variant >= 2 && !can_tile) variant = 1;
-    if constexpr (kD32Type) {
-        if (variant == 12) {        // counting-sort gather (msda_bwd_bins.h); the one-kernel fused form stays with tile_lv
-            const bool will_split = fa.proj != nullptr && opt_bwd_split.load() != 0 &&
-                                    (soft_ok || (workspace != nullptr &&
-                                                 workspace_bytes >= (size_t)N * Lq * M * L * P * 3 * sizeof(float)));
-            if (P > 8 || (fa.proj != nullptr && !will_split)) variant = 10;
-        }
-        if (variant == 10 || variant == 12) {       // one pyramid level per workgroup
-            TilePlan pl;
-            size_t lds_all = 0;
-            BinsPlan bp;
-            memset(&bp, 0, sizeof(bp));
-            int bins_ni = 0;
-            size_t bins_lds = 0;
-            bool planned = false;
-            if (variant == 12) {
-                if (make_tile_plan(pl, shapes_host, N, S, M, D, L, Lq, P, value_bytes, bins_margin, 0, 8, 0, lds_all, false)) {
-                    for (int ni = 2; ni <= 3 && !bins_ni; ++ni)
-                        if (make_bins_plan(bp, pl, ni, bins_lds)) bins_ni = ni;
-                }
-                planned = bins_ni != 0;
-                if (!planned) variant = 10;
-                bp.shrink = bins_shrink;
-                bp.level = sel;
-                // (cumulative counters, fixed addresses: a captured launch counts like an eager one)
-                bp.stats = slot ? slot->dev : nullptr;
-                bp.stats_host = slot ? slot->host_dev : nullptr;
-            }
-            if (!planned)
-                planned = P <= 8 && make_tile_plan(pl, shapes_host, N, S, M, D, L, Lq, P, value_bytes,
-                                                   opt_bwd_tile_margin.load(), 0, 8, 0, lds_all);
-            if (planned) {
-                int win_max = 0;
-                for (int l = 0; l < L; ++l) win_max = pl.win[l] > win_max ? pl.win[l] : win_max;
-                const size_t lds = variant == 12 ? bins_lds
-                                                 : (size_t)(win_max * win_max + 8) * 128 + (size_t)32 * (2 * P + 1) * 16;
-                const int grid = (pl.n_blocks * L + 7) & ~7;
-                PointSrc src = make_src(loc, attn, fa, M, L, P);
-                pl.ablate = opt_bwd_ablate.load();
-                pl.wide_log2 = opt_bwd_wide_log2.load();
-                const long n_rows = (long)N * Lq * M;
-                // Split fused backward (needs the caller's workspace): materialise the prologue once -- the tiled
-                // kernel would otherwise redo the row softmax and the location arithmetic in each of its L
-                // workgroups per region -- run the plain kernel on it, finish the Jacobians in place.
-                const bool soft = soft_ok && variant == 12 && opt_bwd_split.load() != 0;      // (no workspace needed)
-                const bool split = fused && opt_bwd_split.load() != 0 &&
-                                   (soft || (workspace != nullptr && workspace_bytes >= (size_t)n_rows * L * P * 3 * sizeof(float)));
-                // The counting-sort kernel computes the locations itself (one lane per point: the arithmetic is
-                // cheap there) and, for 2-d reference points, writes the final offset gradients: the two side
-                // kernels then move a third of the bytes (attention weights out, the softmax Jacobian in place).
-                const bool slim = split && variant == 12 && L * P <= 16;
-                const int offsets_done = slim && fa.ref_dim == 2 ? 1 : 0;
-                bp.fused_loc = slim ? 1 : 0;
-                bp.offsets_done = offsets_done;
-                bool rows16 = false;
-                bp.soft = soft ? 1 : 0;
-                if (split && !soft) {
-                    float *loc_ws = workspace, *attn_ws = workspace + (size_t)n_rows * L * P * 2;
-                    // one lane per row (16 points as four 16-byte accesses): the slim path's two side kernels
-                    rows16 = slim && L * P == 16 && (fa.proj_stride % 4) == 0 && (src.n_off % 4) == 0 &&
-                             (((uintptr_t)fa.proj | (uintptr_t)grad_proj | (uintptr_t)workspace) & 15) == 0 &&
-                             n_rows < (1L << 31) && opt_bwd_side_rows.load() != 0;
-                    if (rows16) {
-                        hipLaunchKernelGGL(msda_fused_attn16_rows_kernel, dim3(clamp_grid((n_rows + 255) / 256, 32)),
-                                           dim3(256), 0, stream, src, (unsigned)n_rows, (unsigned)M, attn_ws);
-                    } else if (L * P <= 16) {
-                        hipLaunchKernelGGL(msda_fused_points16_kernel, dim3(clamp_grid((n_rows * 16 + 255) / 256, 32)),
-                                           dim3(256), 0, stream, shapes, src, n_rows, M, L, P,
-                                           slim ? (float *)nullptr : loc_ws, attn_ws);
-                    } else {
-                        hipLaunchKernelGGL(msda_fused_points_kernel, dim3(clamp_grid((n_rows * 8 + 255) / 256, 16)),
-                                           dim3(256), 0, stream, shapes, src, n_rows, M, L, P, loc_ws, attn_ws);
-                    }
-                    if ((rc = check_launch("msda_fused_points_kernel"))) return rc;
-                    src.loc = loc_ws;
-                    src.attn = attn_ws;
-                }
-#define MSDA_LAUNCH_LV(PTS, FU, NAME)                                                                                \
-    do {                                                                                                             \
-        rc = allow_big_lds(msda_bwd_d32_tile_lv<PTS, TV, FU>, lds);                                                  \
-        if (rc) return rc;                                                                                           \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_bwd_d32_tile_lv<PTS, TV, FU>), dim3(grid), dim3(kTileThreads), lds, stream, value,  \
-                           lstart, src, grad_out, (float *)grad_value, (float *)grad_loc, (float *)grad_attn,        \
-                           grad_proj, pl);                                                                           \
-    } while (0)
-                const bool b16 = sizeof(TV) == 2;
-#define MSDA_LAUNCH_BINS(NI, NAME)                                                                                   \
-    do {                                                                                                             \
-        g_kernel = NAME;                                                                                             \
-        hipLaunchKernelGGL((msda_bwd_d32_bins<NI, TV>), dim3(grid), dim3(kTileThreads), lds, stream, value, lstart,  \
-                           src, grad_out, (float *)grad_value, (float *)grad_loc, (float *)grad_attn, grad_proj, pl, \
-                           bp, (const TV *)nullptr);                                                                 \
-    } while (0)
-                if (variant == 12 && soft) {       // (fp32, L = P = 4) everything of the fused backward in the one kernel
-                    if constexpr (sizeof(TV) == 4) {
-                        g_kernel = bins_ni == 2 ? "msda_bwd_d32_tile_bins<split,soft>" : "msda_bwd_d32_tile_bins<3,split,soft>";
-                        if (bins_ni == 2)
-                            hipLaunchKernelGGL((msda_bwd_d32_bins<2, TV, true>), dim3(grid), dim3(kTileThreads), lds, stream, value,
-                                               lstart, src, grad_out, (float *)grad_value, (float *)grad_loc, (float *)grad_attn,
-                                               grad_proj, pl, bp, fwd_out);
-                        else
-                            hipLaunchKernelGGL((msda_bwd_d32_bins<3, TV, true>), dim3(grid), dim3(kTileThreads), lds, stream, value,
-                                               lstart, src, grad_out, (float *)grad_value, (float *)grad_loc, (float *)grad_attn,
-                                               grad_proj, pl, bp, fwd_out);
-                    }
-                } else if (variant == 12) {
-                    if (bins_ni == 2) MSDA_LAUNCH_BINS(2, split ? (b16 ? "msda_bwd_d32_tile_bins<bf16,split>" : "msda_bwd_d32_tile_bins<split>")
-                                                                : (b16 ? "msda_bwd_d32_tile_bins<bf16>" : "msda_bwd_d32_tile_bins"));
-                    else MSDA_LAUNCH_BINS(3, split ? (b16 ? "msda_bwd_d32_tile_bins<3,bf16,split>" : "msda_bwd_d32_tile_bins<3,split>")
-                                                   : (b16 ? "msda_bwd_d32_tile_bins<3,bf16>" : "msda_bwd_d32_tile_bins<3>"));
-                } else {
-                    if (split) MSDA_LAUNCH_LV(2, false, b16 ? "msda_bwd_d32_tile_lv<2,bf16,split>" : "msda_bwd_d32_tile_lv<2,split>");
-                    else if (fused) MSDA_LAUNCH_LV(2, true, b16 ? "msda_bwd_d32_tile_lv<2,bf16,fused>" : "msda_bwd_d32_tile_lv<2,fused>");
-                    else MSDA_LAUNCH_LV(2, false, b16 ? "msda_bwd_d32_tile_lv<2,bf16>" : "msda_bwd_d32_tile_lv<2>");
-                }
-#undef MSDA_LAUNCH_LV
-#undef MSDA_LAUNCH_BINS
-                rc = check_launch(g_kernel);
-                if (rc || !fused || soft) return rc;
-                const int jgrid = clamp_grid((n_rows * 8 + 255) / 256, 16);
-                if (split) {
-                    if (rows16 && offsets_done) {
-                        hipLaunchKernelGGL(msda_fused_finish16_rows_kernel, dim3(clamp_grid((n_rows + 255) / 256, 32)),
-                                           dim3(256), 0, stream, src, (unsigned)n_rows, (unsigned)M, grad_proj);
-                    } else if (L * P <= 16) {
-                        hipLaunchKernelGGL(msda_fused_finish16_kernel, dim3(clamp_grid((n_rows * 16 + 255) / 256, 32)),
-                                           dim3(256), 0, stream, shapes, src, n_rows, M, L, P, grad_proj, offsets_done);
-                    } else {
-                        hipLaunchKernelGGL(msda_fused_finish_kernel, dim3(jgrid), dim3(256), 0, stream, shapes, src,
-                                           n_rows, M, L, P, grad_proj);
-                    }
-                    const char *name = g_kernel;
-                    rc = check_launch("msda_fused_finish_kernel");
-                    g_kernel = name;
-                    return rc;
-                }
-                hipLaunchKernelGGL(msda_softmax_jacobian_kernel, dim3(jgrid), dim3(256), 0, stream, src, n_rows, M, L * P,
-                                   grad_proj);
-                const char *name = g_kernel;
-                rc = check_launch("msda_softmax_jacobian_kernel");
-                g_kernel = name;
-                return rc;
-            }
-            variant = 1;
-        }
-    }
-    const long n_rows = (long)N * Lq * M;
-    if constexpr (kD32Type) {
-        // few-query calls at D = 32 (the decoder's cross-attention): 32 lanes per row, grad_value atomics in whole
-        // 128-byte rows, four points in flight (msda_bwd_rows.h)
-        const int requested = opt_bwd_variant.load();      // 1 = the generic kernel, explicitly
-        if (d32_ok(D, L, value_elems) && L * P <= kRowsMaxLP && (opt_bwd_rows.load() != 0 || strided) && n_rows < (1L << 31) &&
-            (requested != 1 || strided)) {
-            const PointSrc src = make_src(loc, attn, fa, M, L, P);
-            // a row is a chain of dependent round trips (stage -> loads -> atomics -> reductions): small calls get one
-            // wavefront (two rows) per workgroup so that every CU holds several chains
-            int threads = opt_bwd_rows_block.load();
-            if (threads != 64 && threads != 128 && threads != 256) threads = n_rows <= 16384 ? 64 : 256;
-            const int per = threads / 32;
-            const int grid = clamp_grid((n_rows + per - 1) / per, 64);
-            const unsigned gv_bytes = (unsigned)(value_elems * 4);
-            const bool b16 = sizeof(TV) == 2;
-            if (fused) {
-                g_kernel = b16 ? "msda_bwd_d32_rows<bf16,fused>" : "msda_bwd_d32_rows<fused>";
-                hipLaunchKernelGGL((msda_bwd_d32_rows<TV, true>), dim3(grid), dim3(threads), 0, stream, value, shapes, lstart,
-                                   src, grad_out, N, S, M, L, Lq, P, (float *)grad_value, (float *)nullptr,
-                                   (float *)nullptr, grad_proj, grad_ref_part, (unsigned)value_bytes, gv_bytes,
-                                   (unsigned *)nullptr, 0u, (unsigned)(strided ? vstride : 0));
-            } else {
-                g_kernel = b16 ? "msda_bwd_d32_rows<bf16>" : "msda_bwd_d32_rows";
-                hipLaunchKernelGGL((msda_bwd_d32_rows<TV, false>), dim3(grid), dim3(threads), 0, stream, value, shapes, lstart,
-                                   src, grad_out, N, S, M, L, Lq, P, (float *)grad_value, (float *)grad_loc,
-                                   (float *)grad_attn, (float *)nullptr, (float *)nullptr, (unsigned)value_bytes, gv_bytes,
-                                   (unsigned *)nullptr, 0u, (unsigned)(strided ? vstride : 0));
-            }
-            return check_launch(g_kernel);
-        }
-    }
-    int block = ((D + 63) / 64) * 64;
-    if (block > 1024) block = 1024;
-    const int grid = (int)(n_rows < 65536L * 16 ? n_rows : 65536L * 16);
-    if constexpr (sizeof(TC) == 4) {
-        if (fused) {
-            const PointSrc src = make_src(loc, attn, fa, M, L, P);
-            g_kernel = "msda_bwd_generic<fused>";
-            hipLaunchKernelGGL((msda_bwd_generic<TV, TC, TG, true>), dim3(grid), dim3(block), 0, stream, value, shapes,
-                               lstart, (const TC *)nullptr, (const TC *)nullptr, src, grad_out, N, S, M, D, L, Lq, P,
-                               grad_value, (TC *)nullptr, (TC *)nullptr, grad_proj, grad_ref_part);
-            return check_launch(g_kernel);
-        }
-    }
-    g_kernel = "msda_bwd_generic";
-    hipLaunchKernelGGL((msda_bwd_generic<TV, TC, TG, false>), dim3(grid), dim3(block), 0, stream, value, shapes, lstart,
-                       loc, attn, PointSrc{}, grad_out, N, S, M, D, L, Lq, P, grad_value, grad_loc, grad_attn,
-                       (float *)nullptr, (float *)nullptr);
-    return check_launch(g_kernel);
+int run_backward(long vstride, const void *value, const int64_t *shapes, const int64_t *lstart, const TC *loc, const TC *attn,
+                 const FusedArgs &fa, const void *grad_out, const void *fwd_out, int N, int S, int M, int D, int L, int Lq,
+                 int P, TG *grad_value, TC *grad_loc, TC *grad_attn, float *grad_proj, float *grad_ref_part,
+                 int zero_grad_value, const int64_t *shapes_host, void *workspace, size_t workspace_bytes, void *stream) {
+    Call<TV, TC, TG> c;
+    c.N = N; c.S = S; c.M = M; c.D = D; c.L = L; c.Lq = Lq; c.P = P;
+    c.shapes = shapes; c.lstart = lstart; c.shapes_host = shapes_host;
+    c.loc = loc; c.attn = attn; c.fa = fa;
+    c.value = (const TV *)value; c.grad_out = (const TV *)grad_out; c.fwd_out = (const TV *)fwd_out;
+    c.grad_value = grad_value; c.grad_loc = grad_loc; c.grad_attn = grad_attn;
+    c.grad_proj = grad_proj; c.grad_ref_part = grad_ref_part; c.zero_grad_value = zero_grad_value;
+    c.workspace = (float *)workspace; c.workspace_bytes = workspace_bytes;
+    c.stream = (hipStream_t)stream; c.vstride = vstride;
+    return backward_impl(c);
+}
+
+FusedArgs fused_args(const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *mask) {
+    FusedArgs fa;
+    fa.proj = proj; fa.proj_stride = proj_stride; fa.ref = ref; fa.ref_dim = ref_dim; fa.mask = mask;
+    return fa;
 }
 
 }  // namespace
@@ -1350,141 +820,77 @@ int msda_selector_reset(void) {
 const char *msda_last_error(void) { return g_err; }
 const char *msda_last_kernel(void) { return g_kernel; }
 
-int msda_forward_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                     const float *attn, int N, int S, int M, int D, int L, int Lq, int P, float *out,
-                     const int64_t *shapes_host, void *stream) {
-    return forward_impl<float, float>(value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, N, S, M, D, L, Lq, P, out,
-                                      shapes_host, (hipStream_t)stream);
-}
-
-int msda_forward_f64(const double *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const double *loc,
-                     const double *attn, int N, int S, int M, int D, int L, int Lq, int P, double *out,
-                     const int64_t *shapes_host, void *stream) {
-    return forward_impl<double, double>(value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, N, S, M, D, L, Lq, P,
-                                        out, shapes_host, (hipStream_t)stream);
-}
-
-int msda_forward_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                      const float *attn, int N, int S, int M, int D, int L, int Lq, int P, uint16_t *out,
-                      const int64_t *shapes_host, void *stream) {
-    return forward_impl<bf16_t, float>((const bf16_t *)value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, N, S, M,
-                                       D, L, Lq, P, (bf16_t *)out, shapes_host, (hipStream_t)stream);
-}
-
-int msda_backward_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                      const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                      float *grad_value, float *grad_loc, float *grad_attn, int zero_grad_value,
-                      const int64_t *shapes_host, void *stream) {
-    return backward_impl<float, float, float>(value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, grad_out, N, S, M,
-                                              D, L, Lq, P, grad_value, grad_loc, grad_attn, nullptr, nullptr,
-                                              zero_grad_value, shapes_host, (hipStream_t)stream);
-}
-
-int msda_backward_f64(const double *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const double *loc,
-                      const double *attn, const double *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                      double *grad_value, double *grad_loc, double *grad_attn, int zero_grad_value,
-                      const int64_t *shapes_host, void *stream) {
-    return backward_impl<double, double, double>(value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, grad_out, N, S,
-                                                 M, D, L, Lq, P, grad_value, grad_loc, grad_attn, nullptr, nullptr,
-                                                 zero_grad_value, shapes_host, (hipStream_t)stream);
-}
-
-int msda_backward_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                       const float *attn, const uint16_t *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                       float *grad_value, float *grad_loc, float *grad_attn, int zero_grad_value,
-                       const int64_t *shapes_host, void *stream) {
-    return backward_impl<bf16_t, float, float>((const bf16_t *)value, shapes_dev, lstart_dev, loc, attn, FusedArgs{},
-                                               (const bf16_t *)grad_out, N, S, M, D, L, Lq, P, grad_value, grad_loc,
-                                               grad_attn, nullptr, nullptr, zero_grad_value, shapes_host,
-                                               (hipStream_t)stream);
-}
-
-// ---- fused prologue entry points ----
-static FusedArgs fused_args(const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *mask) {
-    FusedArgs fa;
-    fa.proj = proj;
-    fa.proj_stride = proj_stride;
-    fa.ref = ref;
-    fa.ref_dim = ref_dim;
-    fa.mask = mask;
-    return fa;
-}
-
-int msda_fused_forward_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *proj,
-                           int proj_stride, const float *ref, int ref_dim, const uint8_t *pad_mask, int N, int S, int M,
-                           int D, int L, int Lq, int P, float *out, const int64_t *shapes_host, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return forward_impl<float, float>(value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                      fused_args(proj, proj_stride, ref, ref_dim, pad_mask), N, S, M, D, L, Lq, P, out,
-                                      shapes_host, (hipStream_t)stream);
-}
-
-int msda_fused_forward_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                            const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *pad_mask,
-                            int N, int S, int M, int D, int L, int Lq, int P, uint16_t *out,
-                            const int64_t *shapes_host, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return forward_impl<bf16_t, float>((const bf16_t *)value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                       fused_args(proj, proj_stride, ref, ref_dim, pad_mask), N, S, M, D, L, Lq, P,
-                                       (bf16_t *)out, shapes_host, (hipStream_t)stream);
-}
-
-int msda_fused_backward_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                            const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *pad_mask,
-                            const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P, float *grad_value,
-                            float *grad_proj, float *grad_ref_part, int zero_grad_value, const int64_t *shapes_host,
-                            void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<float, float, float>(value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                              fused_args(proj, proj_stride, ref, ref_dim, pad_mask), grad_out, N, S, M,
-                                              D, L, Lq, P, grad_value, nullptr, nullptr, grad_proj, grad_ref_part,
-                                              zero_grad_value, shapes_host, (hipStream_t)stream);
-}
-
-int msda_fused_backward_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                             const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *pad_mask,
-                             const uint16_t *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                             float *grad_value, float *grad_proj, float *grad_ref_part, int zero_grad_value,
-                             const int64_t *shapes_host, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<bf16_t, float, float>((const bf16_t *)value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                               fused_args(proj, proj_stride, ref, ref_dim, pad_mask),
-                                               (const bf16_t *)grad_out, N, S, M, D, L, Lq, P, grad_value, nullptr,
-                                               nullptr, grad_proj, grad_ref_part, zero_grad_value, shapes_host,
-                                               (hipStream_t)stream);
-}
-
-// The fused backward given the forward's output of the same call (ABI 6): see backward_impl -- with it the default
-// backward of the encoder's self-attention is ONE kernel (no attention-weight kernel in front, no Jacobian kernel behind).
-int msda_fused_backward_out_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                                const float *proj, int proj_stride, const float *ref, int ref_dim,
-                                const uint8_t *pad_mask, const float *grad_out, const float *fwd_out, int N, int S, int M,
-                                int D, int L, int Lq, int P, float *grad_value, float *grad_proj, float *grad_ref_part,
-                                int zero_grad_value, const int64_t *shapes_host, void *workspace, size_t workspace_bytes,
-                                void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<float, float, float>(value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                              fused_args(proj, proj_stride, ref, ref_dim, pad_mask), grad_out, N, S, M,
-                                              D, L, Lq, P, grad_value, nullptr, nullptr, grad_proj, grad_ref_part,
-                                              zero_grad_value, shapes_host, (hipStream_t)stream, (float *)workspace,
-                                              workspace_bytes, fwd_out);
-}
-
-int msda_fused_backward_out_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                                 const float *proj, int proj_stride, const float *ref, int ref_dim,
-                                 const uint8_t *pad_mask, const uint16_t *grad_out, const uint16_t *fwd_out, int N, int S,
-                                 int M, int D, int L, int Lq, int P, float *grad_value, float *grad_proj,
-                                 float *grad_ref_part, int zero_grad_value, const int64_t *shapes_host, void *workspace,
-                                 size_t workspace_bytes, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<bf16_t, float, float>((const bf16_t *)value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                               fused_args(proj, proj_stride, ref, ref_dim, pad_mask),
-                                               (const bf16_t *)grad_out, N, S, M, D, L, Lq, P, grad_value, nullptr,
-                                               nullptr, grad_proj, grad_ref_part, zero_grad_value, shapes_host,
-                                               (hipStream_t)stream, (float *)workspace, workspace_bytes,
-                                               (const bf16_t *)fwd_out);
-}
-
+// ---- the compute entry points.  Each takes the thread's pending value stride FIRST -- before anything can fail -- so
+//      that the setting never outlives the call it was made for.  The non-_ws forms are the _ws forms without scratch,
+//      the _ws fused forms the _out forms without the forward's output; f32 / bf16 differ by the cast in run_*. ----
+#define MSDA_DIMS int N, int S, int M, int D, int L, int Lq, int P
+#define MSDA_LEVELS const int64_t *shapes_dev, const int64_t *lstart_dev
+#define MSDA_PLAIN_BWD_TAIL(CT, TC) \
+    const CT *grad_out, MSDA_DIMS, TC *grad_value, TC *grad_loc, TC *grad_attn, int zero_grad_value, const int64_t *shapes_host
+#define MSDA_FUSED_HEAD(CT) \
+    const CT *value, MSDA_LEVELS, const float *proj, int proj_stride, const float *ref, int ref_dim, const uint8_t *pad_mask
+#define MSDA_FUSED_BWD_TAIL \
+    MSDA_DIMS, float *grad_value, float *grad_proj, float *grad_ref_part, int zero_grad_value, const int64_t *shapes_host
+// plain operator, forward and backward (SFX f32 / f64 / bf16; CT: the ABI's element type; TV / TC: the kernels')
+#define MSDA_PLAIN_ENTRIES(SFX, CT, TV, TC)                                                                             \
+    int msda_forward_##SFX(const CT *value, MSDA_LEVELS, const TC *loc, const TC *attn, MSDA_DIMS, CT *out,            \
+                           const int64_t *shapes_host, void *stream) {                                                 \
+        const long vstride = take_value_stride();                                                                      \
+        return run_forward<TV, TC>(vstride, value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, N, S, M, D, L, Lq,  \
+                                   P, out, shapes_host, stream);                                                       \
+    }                                                                                                                  \
+    int msda_backward_##SFX(const CT *value, MSDA_LEVELS, const TC *loc, const TC *attn, MSDA_PLAIN_BWD_TAIL(CT, TC),  \
+                            void *stream) {                                                                            \
+        const long vstride = take_value_stride();                                                                      \
+        return run_backward<TV, TC, TC>(vstride, value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, grad_out,      \
+                                        nullptr, N, S, M, D, L, Lq, P, grad_value, grad_loc, grad_attn, nullptr,      \
+                                        nullptr, zero_grad_value, shapes_host, nullptr, 0, stream);                    \
+    }
+MSDA_PLAIN_ENTRIES(f32, float, float, float)
+MSDA_PLAIN_ENTRIES(f64, double, double, double)
+MSDA_PLAIN_ENTRIES(bf16, uint16_t, bf16_t, float)
+// plain backward with scratch, and the fused prologue's forward / backward / backward with scratch / backward given the
+// forward's output of the same call (ABI 6: with it the default backward of the encoder's self-attention is ONE kernel --
+// no attention-weight kernel in front, no Jacobian kernel behind; bwd_pyramid)
+#define MSDA_FUSED_BACKWARD(FWD_OUT, WS, WS_BYTES)                                                                      \
+    const long vstride = take_value_stride();                                                                          \
+    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");                                                      \
+    return run_backward<TV, float, float>(vstride, value, shapes_dev, lstart_dev, nullptr, nullptr,                    \
+                                          fused_args(proj, proj_stride, ref, ref_dim, pad_mask), grad_out, FWD_OUT, N, \
+                                          S, M, D, L, Lq, P, grad_value, nullptr, nullptr, grad_proj, grad_ref_part,   \
+                                          zero_grad_value, shapes_host, WS, WS_BYTES, stream)
+#define MSDA_WS_FUSED_ENTRIES(SFX, CT, TV_)                                                                             \
+    int msda_backward_ws_##SFX(const CT *value, MSDA_LEVELS, const float *loc, const float *attn,                      \
+                               MSDA_PLAIN_BWD_TAIL(CT, float), void *workspace, size_t workspace_bytes, void *stream) {\
+        const long vstride = take_value_stride();                                                                      \
+        return run_backward<TV_, float, float>(vstride, value, shapes_dev, lstart_dev, loc, attn, FusedArgs{},         \
+                                               grad_out, nullptr, N, S, M, D, L, Lq, P, grad_value, grad_loc,          \
+                                               grad_attn, nullptr, nullptr, zero_grad_value, shapes_host, workspace,   \
+                                               workspace_bytes, stream);                                               \
+    }                                                                                                                  \
+    int msda_fused_forward_##SFX(MSDA_FUSED_HEAD(CT), MSDA_DIMS, CT *out, const int64_t *shapes_host, void *stream) {  \
+        const long vstride = take_value_stride();                                                                      \
+        if (!proj) return fail(MSDA_EINVAL, "null pointer argument");                                                  \
+        return run_forward<TV_, float>(vstride, value, shapes_dev, lstart_dev, nullptr, nullptr,                       \
+                                       fused_args(proj, proj_stride, ref, ref_dim, pad_mask), N, S, M, D, L, Lq, P,    \
+                                       out, shapes_host, stream);                                                      \
+    }                                                                                                                  \
+    int msda_fused_backward_##SFX(MSDA_FUSED_HEAD(CT), const CT *grad_out, MSDA_FUSED_BWD_TAIL, void *stream) {        \
+        using TV = TV_;                                                                                                \
+        MSDA_FUSED_BACKWARD(nullptr, nullptr, 0);                                                                      \
+    }                                                                                                                  \
+    int msda_fused_backward_ws_##SFX(MSDA_FUSED_HEAD(CT), const CT *grad_out, MSDA_FUSED_BWD_TAIL, void *workspace,    \
+                                     size_t workspace_bytes, void *stream) {                                           \
+        using TV = TV_;                                                                                                \
+        MSDA_FUSED_BACKWARD(nullptr, workspace, workspace_bytes);                                                      \
+    }                                                                                                                  \
+    int msda_fused_backward_out_##SFX(MSDA_FUSED_HEAD(CT), const CT *grad_out, const CT *fwd_out, MSDA_FUSED_BWD_TAIL, \
+                                      void *workspace, size_t workspace_bytes, void *stream) {                         \
+        using TV = TV_;                                                                                                \
+        MSDA_FUSED_BACKWARD(fwd_out, workspace, workspace_bytes);                                                      \
+    }
+MSDA_WS_FUSED_ENTRIES(f32, float, float)
+MSDA_WS_FUSED_ENTRIES(bf16, uint16_t, bf16_t)
 size_t msda_fused_workspace_bytes(int N, int Lq, int M, int L, int P) {
     if (N < 0 || Lq < 0 || M <= 0 || L <= 0 || P <= 0) return 0;
     return (size_t)N * Lq * M * L * P * 3 * sizeof(float);
@@ -1507,53 +913,6 @@ size_t msda_backward_workspace_bytes(int fused, int N, int S, int M, int D, int 
         if (make_sort_plan(sp, N, S, M, L, Lq, P, (size_t)elem_bytes, nullptr, opt_bwd_sort_qc.load(), opt_bwd_sort_emult.load())) bytes = ((bytes + 255) & ~(size_t)255) + sp.bytes;
     }
     return bytes;
-}
-
-int msda_backward_ws_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                         const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                         float *grad_value, float *grad_loc, float *grad_attn, int zero_grad_value,
-                         const int64_t *shapes_host, void *workspace, size_t workspace_bytes, void *stream) {
-    return backward_impl<float, float, float>(value, shapes_dev, lstart_dev, loc, attn, FusedArgs{}, grad_out, N, S, M,
-                                              D, L, Lq, P, grad_value, grad_loc, grad_attn, nullptr, nullptr,
-                                              zero_grad_value, shapes_host, (hipStream_t)stream, (float *)workspace,
-                                              workspace_bytes);
-}
-
-int msda_backward_ws_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev, const float *loc,
-                          const float *attn, const uint16_t *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                          float *grad_value, float *grad_loc, float *grad_attn, int zero_grad_value,
-                          const int64_t *shapes_host, void *workspace, size_t workspace_bytes, void *stream) {
-    return backward_impl<bf16_t, float, float>((const bf16_t *)value, shapes_dev, lstart_dev, loc, attn, FusedArgs{},
-                                               (const bf16_t *)grad_out, N, S, M, D, L, Lq, P, grad_value, grad_loc,
-                                               grad_attn, nullptr, nullptr, zero_grad_value, shapes_host,
-                                               (hipStream_t)stream, (float *)workspace, workspace_bytes);
-}
-
-int msda_fused_backward_ws_f32(const float *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                               const float *proj, int proj_stride, const float *ref, int ref_dim,
-                               const uint8_t *pad_mask, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
-                               int P, float *grad_value, float *grad_proj, float *grad_ref_part, int zero_grad_value,
-                               const int64_t *shapes_host, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<float, float, float>(value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                              fused_args(proj, proj_stride, ref, ref_dim, pad_mask), grad_out, N, S, M,
-                                              D, L, Lq, P, grad_value, nullptr, nullptr, grad_proj, grad_ref_part,
-                                              zero_grad_value, shapes_host, (hipStream_t)stream, (float *)workspace,
-                                              workspace_bytes);
-}
-
-int msda_fused_backward_ws_bf16(const uint16_t *value, const int64_t *shapes_dev, const int64_t *lstart_dev,
-                                const float *proj, int proj_stride, const float *ref, int ref_dim,
-                                const uint8_t *pad_mask, const uint16_t *grad_out, int N, int S, int M, int D, int L,
-                                int Lq, int P, float *grad_value, float *grad_proj, float *grad_ref_part,
-                                int zero_grad_value, const int64_t *shapes_host, void *workspace,
-                                size_t workspace_bytes, void *stream) {
-    if (!proj) return fail(MSDA_EINVAL, "null pointer argument");
-    return backward_impl<bf16_t, float, float>((const bf16_t *)value, shapes_dev, lstart_dev, nullptr, nullptr,
-                                               fused_args(proj, proj_stride, ref, ref_dim, pad_mask),
-                                               (const bf16_t *)grad_out, N, S, M, D, L, Lq, P, grad_value, nullptr,
-                                               nullptr, grad_proj, grad_ref_part, zero_grad_value, shapes_host,
-                                               (hipStream_t)stream, (float *)workspace, workspace_bytes);
 }
 
 int msda_fused_points_f32(const int64_t *shapes_dev, const float *proj, int proj_stride, const float *ref, int ref_dim,

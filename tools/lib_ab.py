@@ -5,6 +5,13 @@ qualify) and timed on the encoder call, forward fused / plain and (ABI >= 3) bac
 
     python tools/lib_ab.py [--out gpurun_out/lib_ab.txt] [--rounds 3] name=path.so [name=path.so ...]
     (a name ending in "+opt=val,opt=val" applies msda_set_option pairs to that library first)
+
+    python tools/lib_ab.py --bits [--out FILE] base=path.so [name=path.so ...]
+    does not time: it runs a fixed list of small calls (ABI 7 libraries) that between them take every dispatch path,
+    twice through each library, and prints per call the kernel msda_last_kernel() names and, per output tensor, whether
+    the library agrees with the FIRST one.  The rule comes from the first library alone: an output it reproduces bit for
+    bit over its two passes must be bit-equal in the others; one it does not (float atomics into grad_value) may differ
+    by at most twice its own pass-to-pass maximum absolute difference.  Exit status 1 when a call disagrees.
 """
 import argparse
 import ctypes
@@ -41,8 +48,211 @@ def timed(fn, iters=200, min_warm_ms=40.0, batches=5):
     return t[len(t) // 2] * 1e3
 
 
+PYRAMID = [(20, 30), (10, 15), (5, 8), (3, 4)]
+
+
+def bits_cases():
+    """[(name, options, run(lib) -> {output name: tensor})]: the same inputs for every library and pass."""
+    g = torch.Generator().manual_seed(5)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).cuda()        # noqa: E731
+    uni = lambda *shape: torch.rand(*shape, generator=g).cuda()         # noqa: E731
+    stream = torch.cuda.current_stream().cuda_stream
+    spare = torch.zeros(64, device="cuda")      # (an empty tensor has no storage; the library rejects null pointers)
+    ptr = lambda t: None if t is None else (t.data_ptr() or spare.data_ptr())       # noqa: E731
+    cases = []
+
+    def geometry(shapes, M, P, Lq, D=32, N=2, ref_dim=2):
+        L = len(shapes)
+        sh = torch.tensor(shapes, dtype=torch.int64)
+        S = int(sh.prod(1).sum())
+        self_attn = Lq is None
+        Lq = S if self_attn else Lq
+        x = dict(N=N, S=S, M=M, D=D, L=L, Lq=Lq, P=P, ref_dim=ref_dim, hs=sh.contiguous() if self_attn else None,
+                 shapes=sh.cuda(), lstart=torch.cat((sh.new_zeros(1), sh.prod(1).cumsum(0)[:-1])).cuda(),
+                 value=rnd(N, S, M, D), go=rnd(N, Lq, M * D), proj=rnd(N, Lq, 3 * M * L * P))
+        if self_attn:       # reference point = the query's own pixel centre, offsets of a few pixels
+            ref = torch.cat([torch.stack(torch.meshgrid((torch.arange(h) + 0.5) / h, (torch.arange(w) + 0.5) / w,
+                                                        indexing="ij")[::-1], -1).reshape(-1, 2) for h, w in shapes])
+            x["ref"] = ref[None, :, None, :].expand(N, S, L, 2).contiguous().cuda()
+            x["proj"][..., :2 * M * L * P] *= 2.0
+        else:
+            x["ref"] = uni(N, Lq, L, ref_dim) * (1.0 if ref_dim == 2 else 0.4) + 0.05
+        x["attn"] = torch.softmax(x["proj"][..., 2 * M * L * P:].reshape(N, Lq, M, L * P), -1).reshape(N, Lq, M, L, P).contiguous()
+        off = x["proj"][..., :2 * M * L * P].reshape(N, Lq, M, L, P, 2)
+        wh = torch.stack((x["shapes"][:, 1], x["shapes"][:, 0]), -1).float()[None, None, None, :, None, :]
+        x["loc"] = (x["ref"][:, :, None, :, None, :2] + off / wh).contiguous()
+        return x
+
+    def dims(x):
+        return (x["N"], x["S"], x["M"], x["D"], x["L"], x["Lq"], x["P"])
+
+    def add(name, opts, x, kind, dtype=torch.float32, fused=False, ws=False, out=False, ref_grad=False, stride=0):
+        tdt = dtype if dtype != torch.float64 else torch.float64
+        cdt = torch.float64 if dtype == torch.float64 else torch.float32
+        suf = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}[dtype]
+        N, S, M, D, L, Lq, P = dims(x)
+        value, go = x["value"].to(tdt), x["go"].to(tdt)
+        if stride:          # group 1 of a (N, S, stride / (M * D), M, D) tensor
+            wide = rnd(N, S, stride // (M * D), M, D).to(tdt)
+            wide[:, :, 1] = value
+            value = wide[:, :, 1]
+        loc, attn = x["loc"].to(cdt), x["attn"].to(cdt)
+        fwd_out = rnd(N, Lq, M * D).to(tdt) if out else None
+        hs = x["hs"]
+        head = (ptr(value), ptr(x["shapes"]), ptr(x["lstart"]))
+        fargs = (ptr(x["proj"]), x["proj"].shape[2], ptr(x["ref"]), x["ref_dim"], None)
+
+        def run(lib):
+            res = {}
+            if stride:
+                assert lib.msda_next_value_pixel_stride(stride) == 0
+            if kind == "fwd":
+                o = torch.full((N, Lq, M * D), 7.0, dtype=tdt, device="cuda")
+                tail = (N, S, M, D, L, Lq, P, ptr(o), ptr(hs), stream)
+                rc = (getattr(lib, f"msda_fused_forward_{suf}")(*head, *fargs, *tail) if fused else
+                      getattr(lib, f"msda_forward_{suf}")(*head, ptr(loc), ptr(attn), *tail))
+                res["out"] = o
+            else:
+                gdt = torch.float64 if dtype == torch.float64 else torch.float32
+                gv = (torch.zeros(N, S, stride // (M * D), M, D, dtype=gdt, device="cuda") if stride else
+                      torch.full((N, S, M, D), 7.0, dtype=gdt, device="cuda"))
+                gvp = gv[:, :, 1] if stride else gv
+                w = torch.empty(int(lib.msda_backward_workspace_bytes(int(fused), N, S, M, D, L, Lq, P, value.element_size(),
+                                                                      stream)) + 256, dtype=torch.uint8, device="cuda") if ws else None
+                wsa = (ptr(w), w.numel() if ws else 0)
+                res["grad_value"] = gv
+                if fused:
+                    gp = torch.zeros_like(x["proj"])
+                    gr = torch.zeros(N, Lq, M, L, x["ref_dim"], device="cuda") if ref_grad else None
+                    rc = lib.msda_fused_backward_out_f32 if suf == "f32" else lib.msda_fused_backward_out_bf16
+                    rc = rc(*head, *fargs, ptr(go), ptr(fwd_out), N, S, M, D, L, Lq, P, ptr(gvp), ptr(gp), ptr(gr),
+                            0 if stride else 1, ptr(hs), *wsa, stream)
+                    res["grad_proj"] = gp
+                    if ref_grad:
+                        res["grad_ref_part"] = gr
+                else:
+                    gl, ga = torch.zeros_like(loc), torch.zeros_like(attn)
+                    tail = (ptr(go), N, S, M, D, L, Lq, P, ptr(gvp), ptr(gl), ptr(ga), 0 if stride else 1, ptr(hs))
+                    rc = (getattr(lib, f"msda_backward_ws_{suf}")(*head, ptr(loc), ptr(attn), *tail, *wsa, stream) if ws else
+                          getattr(lib, f"msda_backward_{suf}")(*head, ptr(loc), ptr(attn), *tail, stream))
+                    res["grad_loc"], res["grad_attn"] = gl, ga
+            assert rc == 0, (name, lib.msda_last_error())
+            return res
+        cases.append((name, opts, run))
+
+    dec = geometry(PYRAMID, 8, 4, 100)                  # a few queries: gather / rows
+    dec4 = geometry(PYRAMID, 8, 4, 100, ref_dim=4)
+    pyr = geometry(PYRAMID, 8, 4, None)                 # one query per pixel, host shapes: windowed / bins
+    wide = geometry(PYRAMID, 4, 5, None)                # L * P = 20: the wide prologue and finish kernels
+    none = geometry(PYRAMID, 8, 4, 0)
+    f32, f64, b16 = torch.float32, torch.float64, torch.bfloat16
+    for dt, tag in ((f32, "f32"), (b16, "bf16")):
+        add(f"decoder fwd plain {tag}", {}, dec, "fwd", dt)
+        add(f"decoder fwd fused {tag}", {}, dec, "fwd", dt, fused=True)
+        add(f"decoder bwd plain {tag}", {}, dec, "bwd", dt)
+        add(f"decoder bwd fused {tag}", {}, dec, "bwd", dt, fused=True)
+        add(f"pyramid fwd plain {tag}", {}, pyr, "fwd", dt)
+        add(f"pyramid fwd fused {tag}", {}, pyr, "fwd", dt, fused=True)
+        add(f"pyramid bwd plain {tag}", {}, pyr, "bwd", dt)
+        add(f"pyramid bwd fused {tag}", {}, pyr, "bwd", dt, fused=True)
+        add(f"pyramid bwd fused ws {tag}", {}, pyr, "bwd", dt, fused=True, ws=True)
+        add(f"pyramid bwd fused out {tag}", {}, pyr, "bwd", dt, fused=True, out=True)
+        add(f"pyramid bwd fused out ws {tag}", {}, pyr, "bwd", dt, fused=True, out=True, ws=True)
+        add(f"strided fwd fused {tag}", {}, dec, "fwd", dt, fused=True, stride=3 * 8 * 32)
+        add(f"strided bwd fused {tag}", {}, dec, "bwd", dt, fused=True, stride=3 * 8 * 32)
+        add(f"sorted bwd plain ws {tag}", {"bwd_variant": 13}, pyr, "bwd", dt, ws=True)
+        add(f"sorted bwd fused ws {tag}", {"bwd_variant": 13}, pyr, "bwd", dt, fused=True, ws=True)
+    add("generic fwd f64", {}, dec, "fwd", f64)
+    add("generic bwd f64", {}, dec, "bwd", f64)
+    add("decoder bwd fused ref_grad f32", {}, dec4, "bwd", fused=True, ref_grad=True)
+    add("pyramid bwd fused ws ref_grad f32", {}, pyr, "bwd", fused=True, ws=True, ref_grad=True)
+    add("strided fwd plain f32", {}, dec, "fwd", stride=2 * 8 * 32)
+    add("strided bwd plain f32", {}, dec, "bwd", stride=2 * 8 * 32)
+    add("sorted bwd fused ws 4-d ref f32", {"bwd_variant": 13}, dec4, "bwd", fused=True, ws=True)
+    add("sorted bwd fused ws ref_grad f32", {"bwd_variant": 13}, dec4, "bwd", fused=True, ws=True, ref_grad=True)
+    add("sorted without scratch f32", {"bwd_variant": 13}, pyr, "bwd")
+    add("tile_lv bwd plain f32", {"bwd_variant": 10}, pyr, "bwd")
+    add("tile_lv bwd fused f32", {"bwd_variant": 10}, pyr, "bwd", fused=True)
+    add("tile_lv bwd fused ws f32", {"bwd_variant": 10}, pyr, "bwd", fused=True, ws=True)
+    add("bins forced bwd fused ws f32", {"bwd_variant": 12}, pyr, "bwd", fused=True, ws=True)
+    add("bwd_variant 1 f32", {"bwd_variant": 1}, pyr, "bwd")
+    add("bwd_variant 5 f32", {"bwd_variant": 5}, pyr, "bwd")
+    add("bwd_variant 5 decoder f32", {"bwd_variant": 5}, dec, "bwd")
+    for v in (1, 3, 12):
+        add(f"fwd_variant {v} pyramid plain f32", {"fwd_variant": v}, pyr, "fwd")
+        add(f"fwd_variant {v} pyramid fused f32", {"fwd_variant": v}, pyr, "fwd", fused=True)
+    add("fwd_variant 12 decoder f32", {"fwd_variant": 12}, dec, "fwd")
+    add("selector level 1 bwd fused ws f32", {"sel_level": 1}, pyr, "bwd", fused=True, ws=True)
+    add("selector level 2 bwd fused ws f32", {"sel_level": 2}, pyr, "bwd", fused=True, ws=True)
+    add("selector level 2 bwd plain f32", {"sel_level": 2}, pyr, "bwd")
+    add("selector level 1 fwd fused f32", {"sel_level": 1}, pyr, "fwd", fused=True)
+    add("wide fwd fused f32", {}, wide, "fwd", fused=True)
+    add("wide bwd fused f32", {}, wide, "bwd", fused=True)
+    add("wide bwd fused ws f32", {}, wide, "bwd", fused=True, ws=True)
+    add("wide tile_lv bwd fused ws f32", {"bwd_variant": 10}, wide, "bwd", fused=True, ws=True)
+    add("wide sorted bwd fused ws f32", {"bwd_variant": 13}, wide, "bwd", fused=True, ws=True)
+    add("Lq = 0 fwd f32", {}, none, "fwd")
+    add("Lq = 0 bwd f32", {}, none, "bwd")
+    add("Lq = 0 bwd fused f32", {}, none, "bwd", fused=True)
+    return cases
+
+
+def bits_main(args):
+    from memotr_amd._lib import SYMBOLS
+    cases = bits_cases()
+    libs = []
+    for spec in args.libs:
+        name, path = spec.split("=", 1)
+        lib = ctypes.CDLL(os.path.abspath(path))
+        for sym, (argtypes, restype) in SYMBOLS.items():
+            fn = getattr(lib, sym)
+            fn.argtypes, fn.restype = argtypes, restype
+        libs.append((name, lib))
+    runs = {}               # (library, pass) -> [(kernel, {output: tensor})]
+    for name, lib in libs:
+        for p in range(2):
+            assert lib.msda_selector_reset() == 0
+            rec = []
+            for cname, opts, run in cases:
+                for k, v in opts.items():
+                    assert lib.msda_set_option(k.encode(), v) == 0, (k, v)
+                res = run(lib)
+                torch.cuda.synchronize()
+                rec.append((lib.msda_last_kernel().decode(), {k: t.clone() for k, t in res.items()}))
+                for k in opts:
+                    assert lib.msda_set_option(k.encode(), -1 if k == "sel_level" else 0) == 0
+            runs[name, p] = rec
+    base = libs[0][0]
+    diff = lambda a, b: float((a.double() - b.double()).abs().max()) if a.numel() else 0.0       # noqa: E731
+    lines = ["| call | kernel (" + base + ") | output | " + base + " pass 1 vs 2 | " +
+             " | ".join(f"{n} vs {base}" for n, _ in libs[1:]) + " |", "|---|---|---|---|" + "---|" * (len(libs) - 1)]
+    bad = 0
+    for i, (cname, _, _) in enumerate(cases):
+        k0, o0 = runs[base, 0][i]
+        for j, key in enumerate(o0):
+            same0 = torch.equal(o0[key], runs[base, 1][i][1][key])
+            own = diff(o0[key], runs[base, 1][i][1][key])
+            cells = []
+            for n, _ in libs[1:]:
+                kn, on = runs[n, 0][i]
+                eq, d = torch.equal(o0[key], on[key]), diff(o0[key], on[key])
+                ok = kn == k0 and (eq if same0 else d <= 2.0 * own)
+                bad += not ok
+                cells.append(("bit-equal" if eq else f"max abs diff {d:.3e}") + ("" if kn == k0 else f", KERNEL {kn}") +
+                             (" ok" if ok else " FAIL"))
+            lines.append(f"| {cname if j == 0 else ''} | {k0 if j == 0 else ''} | {key} | " +
+                         ("bit-equal" if same0 else f"max abs diff {own:.3e}") + " | " + " | ".join(cells) + " |")
+    lines.append("")
+    lines.append(f"{len(cases)} calls, {bad} disagreements")
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bits", action="store_true", help="compare outputs and kernel names instead of timing (see above)")
     ap.add_argument("--out", default="gpurun_out/lib_ab.txt")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1)
@@ -50,6 +260,8 @@ def main():
     ap.add_argument("libs", nargs="+")
     args = ap.parse_args()
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    if args.bits:
+        sys.exit(bits_main(args))
     x = make_inputs(device="cuda", batch=args.batch)
     f = to_fused_inputs(x)
     N, S, M, D = x["value"].shape
