@@ -28,7 +28,8 @@ const char *clipops_last_error(void);
  *   cost[l,q,t] = w_bbox * |box[l,q] - gt_box[t]|_1 + w_class * (pos - neg)(sigmoid(logit[l,q,gt_label[t]]))
  *                 + w_giou * (-GIoU(xyxy(box[l,q]), xyxy(gt_box[t])))
  * logits: element (l,q,k) at logits[l*logit_sl + q*logit_sq + k]; boxes: (l,q,c) at boxes[l*box_sl + q*box_sq + c]
- * (cxcywh).  gt_labels (T) int64, gt_boxes (T,4) and cost (n_layers,Q,T) are contiguous. */
+ * (cxcywh).  gt_labels (T) int64, gt_boxes (T,4) and cost (n_layers,Q,T) are contiguous.  A label outside [0, K) is
+ * clamped into it (the reference's index would wrap or raise); T == 0 is a no-op. */
 int clipops_match_cost_f32(const float *logits, long logit_sl, long logit_sq, const float *boxes, long box_sl,
                            long box_sq, const int64_t *gt_labels, const float *gt_boxes, int n_layers, int Q, int K,
                            int T, float w_class, float w_bbox, float w_giou, float *cost, void *stream);
@@ -37,6 +38,9 @@ int clipops_match_cost_f32(const float *logits, long logit_sl, long logit_sq, co
  * none).sum(-1) and 1 - diag(generalized_box_iou(xyxy(pred), xyxy(tgt)))).
  * Prediction i is row  lay[i]*row_mul + row_add + qidx[i]  of `boxes` (rows of 4 floats, cxcywh); target i is row
  * gidx[i] of tgt_boxes (gidx == NULL: row i).  weight (n) may be NULL; both outputs are multiplied by it. */
+/* (The backward follows torch's autograd where the function has a kink: a max / min of two equal corners passes half the
+ * gradient to each side, clamp(min=0) passes it at exactly 0, |x| has slope 0 at 0 -- held to float64 autograd on boxes
+ * that tie, share an edge or share a corner by tests/test_clip_ops_truth_gpu.py.) */
 int clipops_pair_box_loss_fwd_f32(const float *boxes, const int64_t *lay, const int64_t *qidx, long row_mul,
                                   long row_add, const float *tgt_boxes, const int64_t *gidx, const float *weight,
                                   int n, float *l1, float *giou_loss, void *stream);
@@ -72,7 +76,10 @@ int clipops_focal_labels_i64(const int64_t *lay, const int64_t *q, const int64_t
 /* Sigmoid focal loss of stacked layers (reference models/criterion.py:442-467, RetinaNet form): per layer l
  *   loss[l] = sum_q mean_k  a_t * ce * (1 - p_t)^gamma,   target one-hot of labels[l,q] (label == K: background).
  * logits element (l,q,k) at logits[l*sl + q*sq + k]; labels (n_layers,Nq) int64 contiguous; loss (n_layers).
- * One workgroup per layer with a fixed-order reduction: results are run-to-run identical. */
+ * One workgroup per layer with a fixed-order reduction: results are run-to-run identical.  alpha < 0: no a_t weight.
+ * Any gamma >= 1 and gamma == 0 are differentiated (gamma == 0: the modulating factor is constant, its derivative zero
+ * even where 1 - p_t has rounded to 0); 0 < gamma < 1 has an infinite derivative there and is not supported.  Finite for
+ * every finite logit (held on [-90, 90], past the overflow of expf at 88.72). */
 int clipops_focal_fwd_f32(const float *logits, long sl, long sq, const int64_t *labels, int n_layers, int Nq, int K,
                           float alpha, float gamma, float *loss, void *stream);
 /* grad_logits (n_layers,Nq,K) contiguous = grad_loss[l] * d loss[l] / d logit. */
@@ -101,7 +108,9 @@ int clipops_refine_boxes_bwd_f32(const float *out, const float *ref, const float
 
 /* Column sums of a small row-major matrix: out[c] = sum_r x[r*cols + c] -- the bias gradient of a Linear over a few
  * hundred query rows.  torch's generic reduction takes 12-17 us for 310 x 256 .. 2048 on MI355X (one of ~400 such calls
- * per train step); this one tiles 32 columns x 8 row lanes per workgroup and sums in a fixed order. */
+ * per train step); this one tiles 32 columns x 8 row lanes per workgroup and sums in a fixed order.  All column-sum
+ * entry points accumulate in fp64 and round once (error <= half an ulp of the result + the rounding of the partials in
+ * the two-pass forms), whatever the cancellation between rows. */
 int clipops_colsum_f32(const float *x, long rows, int cols, float *out, void *stream);
 /* First pass for tall matrices: partial[k*cols + c] = sum of rows [k*chunk_rows, (k+1)*chunk_rows) of column c,
  * k < ceil(rows / chunk_rows); clipops_colsum_f32 over `partial` finishes (fixed order end to end). */
@@ -117,14 +126,19 @@ int clipops_colsum_partial_bf16(const uint16_t *x, long rows, int cols, int chun
  * query row), K and V of a head staged in LDS.  q / k / v are addressed as base + b*batch_stride + i*row_stride + h*32
  * (element strides), so the packed (B, L, 2E) projection of q and k needs no copy; key_mask (B, L) bytes, non-zero =
  * ignore that key, may be NULL; out (B, L, H*32) contiguous; lse (B, H, L) receives max + log(sum) per row for the
- * backward.  Replaces the AOTriton kernels behind F.scaled_dot_product_attention on this path. */
+ * backward.  Replaces the AOTriton kernels behind F.scaled_dot_product_attention on this path.
+ * A (batch, row) whose keys are ALL masked has no softmax: its out is NaN (0 * inf, what torch's softmax over -inf gives
+ * too), its lse -inf, and the backward gives it and its keys zero gradients; other batches of the call are unaffected
+ * bit for bit.  A row with ONE live key gets that key's v bit for bit. */
 #define CLIPOPS_MHA_MAX_L 512
 int clipops_mha_fwd_f32(const float *q, const float *k, const float *v, long q_bs, long q_rs, long k_bs, long k_rs,
                         long v_bs, long v_rs, const uint8_t *key_mask, int B, int H, int L, float scale, float *out,
                         float *lse, void *stream);
 /* Gradients of the above.  grad_out (B, L, H*32) contiguous; grad_q / grad_k / grad_v are addressed like q / k / v
  * (each its own batch / row stride, so grad_q and grad_k can be the two halves of one (B, L, 2E) buffer).  Two kernels:
- * one by query rows (grad_q), one by key rows (grad_k, grad_v); probabilities are recomputed from lse. */
+ * one by query rows (grad_q), one by key rows (grad_k, grad_v); probabilities are recomputed from lse, from the forward's
+ * own score bits ((q * scale) . k in one summation order everywhere), and dO . O is summed in the order of dO . v: a row
+ * with one live key gets grad_q = 0 and its key grad_k = 0 exactly, grad_v = the sum of dO.  Masked keys get exact zeros. */
 int clipops_mha_bwd_f32(const float *q, const float *k, const float *v, long q_bs, long q_rs, long k_bs, long k_rs,
                         long v_bs, long v_rs, const uint8_t *key_mask, const float *out, const float *lse,
                         const float *grad_out, int B, int H, int L, float scale, float *grad_q, long gq_bs, long gq_rs,

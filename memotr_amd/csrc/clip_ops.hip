@@ -33,6 +33,7 @@ int check_launch(const char *what) {
 }
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef double f64x4_t __attribute__((ext_vector_type(4)));
 
 struct Box {
     float x1, y1, x2, y2;
@@ -222,7 +223,9 @@ __device__ __forceinline__ Focal focal_elem(float x, bool is_pos, float alpha, f
     Focal f;
     f.loss = a_t * (ce * mod);
     // d/dx: -s a_t [gamma q^(gamma-1) (p_t q) ce + q^gamma q],  s = +1 (positive) / -1
-    const float qg1 = gamma == 2.f ? q : powf(q, gamma - 1.f);
+    // (gamma == 0: the modulating factor is the constant 1 and has no derivative -- torch's pow backward returns zero
+    //  there; q^(gamma-1) would be 1/q, infinite once p_t saturates at 1, and 0 * inf a NaN)
+    const float qg1 = gamma == 2.f ? q : (gamma == 0.f ? 0.f : powf(q, gamma - 1.f));
     const float d = a_t * (gamma * qg1 * (p_t * q) * ce + mod * q);
     f.dloss = is_pos ? -d : d;
     return f;
@@ -349,13 +352,16 @@ __global__ __launch_bounds__(256) void refine_boxes_bwd_kernel(const float *__re
     }
 }
 
-// 32 columns x 8 row lanes per workgroup; lane (ty, tx) sums rows ty, ty + 8, ... of column tile tx
+// 32 columns x 8 row lanes per workgroup; lane (ty, tx) sums rows ty, ty + 8, ... of column tile tx.
+// The sums of all column-sum kernels are kept in fp64 and rounded once: a lane's rows are a strided subset, so an fp32
+// partial sum grows to (rows / lanes) * max|x| even where neighbouring rows cancel, and its rounding error with it
+// (alternating +-1e4 over 2048 rows: 0.3 absolute against a true sum of ~50).  The kernels are bound by their loads.
 __global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ x, long rows, int cols,
                                                     float *__restrict__ out) {
-    __shared__ float s_part[8][33];
+    __shared__ double s_part[8][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + tx;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
     if (c < cols) {
         long r = ty;
         for (; r + 24 < rows; r += 32) {          // four independent loads in flight
@@ -369,10 +375,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ x
     s_part[ty][tx] = (a0 + a1) + (a2 + a3);
     __syncthreads();
     if (ty == 0 && c < cols) {
-        float t = s_part[0][tx];
+        double t = s_part[0][tx];
 #pragma unroll
         for (int i = 1; i < 8; ++i) t += s_part[i][tx];
-        out[c] = t;
+        out[c] = (float)t;
     }
 }
 
@@ -381,10 +387,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ x
 // and one LDS step over the four wavefronts.  6.0 -> ~3 us at 310 x 256 against the 32 x 8 tile above.
 __global__ __launch_bounds__(256) void colsum_quad_kernel(const float *__restrict__ x, long rows, int cols,
                                                          float *__restrict__ out) {
-    __shared__ f32x4_t s_w[4];
+    __shared__ f64x4_t s_w[4];
     const int c = blockIdx.x * 4;
-    f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-    for (long r = threadIdx.x; r < rows; r += 256) a += *reinterpret_cast<const f32x4_t *>(x + r * cols + c);
+    f64x4_t a = {0., 0., 0., 0.};
+    for (long r = threadIdx.x; r < rows; r += 256) {
+        const f32x4_t v = *reinterpret_cast<const f32x4_t *>(x + r * cols + c);
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         a.x += __shfl_xor(a.x, o, 64);
@@ -394,7 +403,11 @@ __global__ __launch_bounds__(256) void colsum_quad_kernel(const float *__restric
     }
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = a;
     __syncthreads();
-    if (threadIdx.x == 0) *reinterpret_cast<f32x4_t *>(out + c) = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    if (threadIdx.x == 0) {
+        const f64x4_t t = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+        const f32x4_t r = {(float)t.x, (float)t.y, (float)t.z, (float)t.w};
+        *reinterpret_cast<f32x4_t *>(out + c) = r;
+    }
 }
 
 // the same tile over one chunk of rows per workgroup row (blockIdx.y): partial sums for tall matrices
@@ -406,12 +419,12 @@ __device__ __forceinline__ float colsum_ld(const uint16_t *x, long i) {      // 
 template <typename TX>
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const TX *__restrict__ x, long rows, int cols,
                                                             int chunk_rows, float *__restrict__ partial) {
-    __shared__ float s_part[8][33];
+    __shared__ double s_part[8][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + tx;
     const long r0 = (long)blockIdx.y * chunk_rows;
     const long r1 = r0 + chunk_rows < rows ? r0 + chunk_rows : rows;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
     if (c < cols) {
         long r = r0 + ty;
         for (; r + 24 < r1; r += 32) {
@@ -425,10 +438,10 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const TX *__restric
     s_part[ty][tx] = (a0 + a1) + (a2 + a3);
     __syncthreads();
     if (ty == 0 && c < cols) {
-        float t = s_part[0][tx];
+        double t = s_part[0][tx];
 #pragma unroll
         for (int i = 1; i < 8; ++i) t += s_part[i][tx];
-        partial[(long)blockIdx.y * cols + c] = t;
+        partial[(long)blockIdx.y * cols + c] = (float)t;
     }
 }
 
@@ -441,12 +454,12 @@ template <typename TX>
 __global__ __launch_bounds__(256) void relu_bwd_colsum_partial_kernel(const TX *__restrict__ g, const TX *__restrict__ y,
                                                                      long rows, int cols, int chunk_rows,
                                                                      TX *__restrict__ g2, float *__restrict__ partial) {
-    __shared__ float s_part[8][33];
+    __shared__ double s_part[8][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + tx;
     const long r0 = (long)blockIdx.y * chunk_rows;
     const long r1 = r0 + chunk_rows < rows ? r0 + chunk_rows : rows;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
     if (c < cols) {
         long r = r0 + ty;
         for (; r + 24 < r1; r += 32) {
@@ -468,10 +481,10 @@ __global__ __launch_bounds__(256) void relu_bwd_colsum_partial_kernel(const TX *
     s_part[ty][tx] = (a0 + a1) + (a2 + a3);
     __syncthreads();
     if (ty == 0 && c < cols) {
-        float t = s_part[0][tx];
+        double t = s_part[0][tx];
 #pragma unroll
         for (int i = 1; i < 8; ++i) t += s_part[i][tx];
-        partial[(long)blockIdx.y * cols + c] = t;
+        partial[(long)blockIdx.y * cols + c] = (float)t;
     }
 }
 
@@ -505,6 +518,20 @@ __device__ __forceinline__ float dot32(const float *a, const float *lds_row) {
         s1 = fmaf(a[4 * i + 1], v.y, s1);
         s0 = fmaf(a[4 * i + 2], v.z, s0);
         s1 = fmaf(a[4 * i + 3], v.w, s1);
+    }
+    return s0 + s1;
+}
+
+// the same sum from two register rows.  D = dO . O of the backward uses the association of dot32 on purpose: where a
+// row attends to ONE key (L = 1, a single live key) O is that key's V bit for bit, and dO . V_j - D must be exactly zero
+__device__ __forceinline__ float dot32r(const float *a, const float *b) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        s0 = fmaf(a[4 * i], b[4 * i], s0);
+        s1 = fmaf(a[4 * i + 1], b[4 * i + 1], s1);
+        s0 = fmaf(a[4 * i + 2], b[4 * i + 2], s0);
+        s1 = fmaf(a[4 * i + 3], b[4 * i + 3], s1);
     }
     return s0 + s1;
 }
@@ -612,8 +639,7 @@ __global__ __launch_bounds__(256) void mha_bwd_q_kernel(const float *__restrict_
     {
         float orr[kHd];
         load_row32(out + orow, orr);
-#pragma unroll
-        for (int i = 0; i < kHd; ++i) D = fmaf(gr[i], orr[i], D);
+        D = dot32r(gr, orr);
     }
 #pragma unroll
     for (int i = 0; i < kHd; ++i) { qr[i] *= scale; acc[i] = 0.f; }
@@ -647,15 +673,21 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float *__restrict
     float *s_lse = Gs + (size_t)L * kPitch, *s_D = s_lse + L;
     const int h = blockIdx.y, b = blockIdx.z;
     stage_rows(Qs, q + b * q_bs + h * kHd, q_rs, L);
+    // Q is kept SCALED, as the forward and grad_q hold it: (q * scale) . k is then the forward's score bit for bit and
+    // exp(s - lse) the forward's probability (scaling k instead moved s by an ulp: p = 1 +- 5e-7 where it is exactly 1).
+    // Each thread scales the float4s it staged itself, so no barrier is needed in between.
+    for (int i = threadIdx.x; i < L * 8; i += blockDim.x) {
+        f32x4_t *p4 = reinterpret_cast<f32x4_t *>(Qs + (i >> 3) * kPitch + (i & 7) * 4);
+        *p4 = *p4 * scale;
+    }
     stage_rows(Gs, go + (long)b * L * (H * kHd) + h * kHd, (long)H * kHd, L);
     for (int i = threadIdx.x; i < L; i += blockDim.x) s_lse[i] = lse[((long)b * H + h) * L + i];
     __syncthreads();
     for (int i = threadIdx.x; i < L; i += blockDim.x) {             // D_i = dO_i . O_i
         const float *o = out + ((long)b * L + i) * (H * kHd) + h * kHd;
-        float d = 0.f;
-#pragma unroll
-        for (int c = 0; c < kHd; ++c) d = fmaf(Gs[i * kPitch + c], o[c], d);
-        s_D[i] = d;
+        float orr[kHd];
+        load_row32(o, orr);
+        s_D[i] = dot32(orr, Gs + i * kPitch);
     }
     __syncthreads();
     const int row = blockIdx.x * kRows + threadIdx.x / kLanes, sub = threadIdx.x % kLanes;
@@ -666,7 +698,7 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float *__restrict
     load_row32(k + b * k_bs + rowc * k_rs + h * kHd, kr);
     load_row32(v + b * v_bs + rowc * v_rs + h * kHd, vr);
 #pragma unroll
-    for (int i = 0; i < kHd; ++i) { kr[i] *= scale; ak[i] = 0.f; av[i] = 0.f; }
+    for (int i = 0; i < kHd; ++i) { ak[i] = 0.f; av[i] = 0.f; }
     if (!dead) {
         for (int i = sub; i < L; i += kLanes) {
             const float p = expf(dot32(kr, Qs + i * kPitch) - s_lse[i]);
@@ -678,7 +710,7 @@ __global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float *__restrict
     float *pk = gk + b * gk_bs + rowc * gk_rs + h * kHd, *pv = gv + b * gv_bs + rowc * gv_rs + h * kHd;
 #pragma unroll
     for (int i = 0; i < kHd; ++i) {
-        const float tk = sum8l(ak[i]) * scale, tv = sum8l(av[i]);
+        const float tk = sum8l(ak[i]), tv = sum8l(av[i]);           // (ak sums ds * (q * scale) already)
         if (row_ok && (i >> 2) == sub) {
             pk[i] = tk;
             pv[i] = tv;

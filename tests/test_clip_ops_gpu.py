@@ -91,8 +91,9 @@ def test_pair_box_loss_edge_cases():
         res[name] = (l1.detach(), gl.detach(), x.grad)
     torch.testing.assert_close(res["kernel"][0], res["torch"][0], rtol=1e-6, atol=1e-7)
     torch.testing.assert_close(res["kernel"][1], res["torch"][1], rtol=1e-5, atol=1e-6)
-    # the exact match (pair 2) sits on max/min ties, where torch halves the sub-gradient: rows 0, 1, 3 compared
-    torch.testing.assert_close(res["kernel"][2][0, 0, [0, 1, 3]], res["torch"][2][0, 0, [0, 1, 3]], rtol=2e-5, atol=2e-6)
+    # the exact match (pair 2) sits on max/min ties, where torch halves the sub-gradient and so does the kernel
+    # (tests/test_clip_ops_truth_gpu.py holds the tie rows to float64 autograd): all four rows compared
+    torch.testing.assert_close(res["kernel"][2][0, 0], res["torch"][2][0, 0], rtol=2e-5, atol=2e-6)
     assert torch.isfinite(res["kernel"][2]).all()
 
 
