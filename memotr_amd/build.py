@@ -1,6 +1,6 @@
 """Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
-step), libframe_ops_hip.so (raw-frame resize / normalise) and libaugment_ops_hip.so (training-clip augmentation) with
-hipcc for gfx950 (cross-compiles without a GPU)."""
+step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation) and
+libstatic_clip_ops_hip.so (clips made from one still image) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -27,6 +27,9 @@ FRAME_LIB = os.path.join(LIB_DIR, "libframe_ops_hip.so")
 AUGMENT_SRC = os.path.join(_HERE, "csrc", "augment_ops.hip")
 AUGMENT_HDR = os.path.join(os.path.dirname(_HERE), "include", "augment_ops_hip.h")
 AUGMENT_LIB = os.path.join(LIB_DIR, "libaugment_ops_hip.so")
+STATIC_CLIP_SRC = os.path.join(_HERE, "csrc", "static_clip_ops.hip")
+STATIC_CLIP_HDR = os.path.join(os.path.dirname(_HERE), "include", "static_clip_ops_hip.h")
+STATIC_CLIP_LIB = os.path.join(LIB_DIR, "libstatic_clip_ops_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -96,8 +99,15 @@ def build_augment_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(AUGMENT_SRC, AUGMENT_LIB, verbose)
 
 
+def build_static_clip_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(STATIC_CLIP_LIB, (STATIC_CLIP_SRC, STATIC_CLIP_HDR)):
+        return STATIC_CLIP_LIB
+    return _compile(STATIC_CLIP_SRC, STATIC_CLIP_LIB, verbose)
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
     print(build_frame_lib(force=True, verbose=True))
     print(build_augment_lib(force=True, verbose=True))
+    print(build_static_clip_lib(force=True, verbose=True))

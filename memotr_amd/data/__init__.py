@@ -1,3 +1,5 @@
 """Input side: raw decoded frames to the padded normalised batch the model reads (frames.py, the per-frame path) and
-the training-clip augmentation (augment.py)."""
+the training-clip augmentation (augment.py), for clips of a sequence and for clips made from one still image
+(static_clip.py)."""
 from .augment import augment_clip, clip_batch  # noqa: F401
+from .static_clip import augment_static_clip  # noqa: F401

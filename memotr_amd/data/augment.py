@@ -180,20 +180,29 @@ def resample_cpu(frames: torch.Tensor, tables_x, tables_y, flip: bool = False, s
 class ClipAugment:
     """The random decisions of one clip.  ``first``: (h1, w1) of the crop branch's first resize; ``crop``:
     (i, j, ch, cw), top, left, height, width inside the ``first``-resized frame; ``final``: (th, tw); ``hsv``:
-    (dh, ds, dv) or None for no round trip at all; ``reverse``: the clip's frames and infos come out last first."""
+    (dh, ds, dv) or None for no round trip at all; ``reverse``: the clip's frames and infos come out last first.
+    ``shift``: (dx, dy) of a clip made from one still image and ``shift_reverse``, that stage's own reversal; read by
+    ``static_clip.augment_static_clip`` only."""
     flip: bool
     first: Optional[Tuple[int, int]]
     crop: Optional[Tuple[int, int, int, int]]
     final: Tuple[int, int]
     hsv: Optional[Tuple[int, int, int]] = None
     reverse: bool = False
+    shift: Optional[Tuple[int, int]] = None
+    shift_reverse: bool = False
 
 
 def sample_clip_augment(h: int, w: int, rng, np_rng, *, coco_size: bool = False, reverse_clip: float = 0.0,
-                        scales: Sequence[int] = SCALES, max_size: int = 1536) -> ClipAugment:
+                        scales: Sequence[int] = SCALES, max_size: int = 1536,
+                        max_shift: Optional[int] = None) -> ClipAugment:
     """A plan for ``h`` x ``w`` frames with the decision structure of the reference's ``transfroms_for_train``.
     ``rng``: a ``random.Random``, ``np_rng``: a ``np.random.RandomState``.  (The draws are not the reference's draws:
-    it reads the global generators of three libraries.)"""
+    it reads the global generators of three libraries.)  ``max_shift`` (the reference's ``MultiRandomShift`` has 50):
+    the plan of a clip made from one still image, ``|dx|`` and ``|dy|`` uniform in 1 .. max_shift, fair signs and a
+    fair ``shift_reverse``, drawn after everything else; None draws nothing more and gives the plans it always gave."""
+    if max_shift is not None and max_shift < 1:
+        raise ValueError(f"max_shift must be at least 1, got {max_shift}")
     flip = rng.random() < 0.5
     first = crop = None
     if rng.random() < 0.5:
@@ -211,7 +220,13 @@ def sample_clip_augment(h: int, w: int, rng, np_rng, *, coco_size: bool = False,
     gains = gains * np_rng.randint(0, 2, 3)
     hsv = tuple(int(x) for x in gains.astype(np.int16))
     reverse = rng.random() < reverse_clip
-    return ClipAugment(flip=flip, first=first, crop=crop, final=final, hsv=hsv, reverse=reverse)
+    shift, shift_reverse = None, False
+    if max_shift is not None:
+        dx = rng.randint(1, max_shift) * (1 if rng.random() < 0.5 else -1)
+        dy = rng.randint(1, max_shift) * (1 if rng.random() < 0.5 else -1)
+        shift, shift_reverse = (dx, dy), rng.random() < 0.5
+    return ClipAugment(flip=flip, first=first, crop=crop, final=final, hsv=hsv, reverse=reverse, shift=shift,
+                       shift_reverse=shift_reverse)
 
 
 def _branch(plan: ClipAugment, h: int, w: int):

@@ -1,6 +1,7 @@
 """Training-clip augmentation of a 5-frame 1080p clip on one MI355X (results: profiles/clip_augment.md).
 
     python tools/bench_augment.py [--launches 50] [--cpu-repeats 3] [--threads 2]
+    python tools/bench_augment.py --static [--launches 50]         (results: profiles/static_clip.md)
 
 GPU (each step is one child process, started once under its own time limit; the first that fails ends the run):
   plain  HIP-event time of ``augment_clip`` for the plain branch (flip, 1080x1920 -> 800x1422, HSV), one launch,
@@ -10,6 +11,12 @@ GPU (each step is one child process, started once under its own time limit; the 
 Host (this process, ``--threads`` torch threads; a rank has 2 CPUs):
   the host statement of the same two plans, and where PIL imports the reference's chain on PIL images (transpose,
   resize, crop, resize; one thread, without its cv2 HSV step, which is not available).
+--static (one child process, nothing else runs): a 5-frame clip made from ONE 1080p image (data/static_clip.py),
+  chain  HIP-event time of ``shift_chain`` with dx = -37, dy = 23: one launch for the whole clip;
+  copy   a stock device copy of its 31 MB output, the floor;
+  steps  for dx = +37 (no column move: the only sign the resize kernel can express) the same frames made by T - 1
+         dependent ``augops_resample_u8`` launches, each reading the frame before it, with and without the copy that
+         puts the image into frame 0; checked equal to the chain's frames before anything is timed.
 Prints one JSON line.  No time here is a pass / fail condition."""
 import argparse
 import json
@@ -86,6 +93,48 @@ def gpu_step(name, launches):
             "clips_per_s": 1e3 / km, "frames_per_s": T * 1e3 / km}
 
 
+def static_step(launches):
+    from memotr_amd import _augment_lib, _static_clip_lib
+    from memotr_amd.data import augment as A
+    from memotr_amd.data import static_clip as S
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_augment.py needs a GPU")
+    dx, dy = -37, 23
+    img = torch.from_numpy(np.random.RandomState(0).randint(0, 256, (H, W, 3), dtype=np.uint8)).cuda()
+    out = torch.empty((T, H, W, 3), dtype=torch.uint8, device="cuda")
+    dst, steps = torch.empty_like(out), torch.empty_like(out)
+    big = torch.empty(128 << 20, dtype=torch.float32, device="cuda")        # 512 MiB: also leaves everything cold in cache
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tx, ty = A._device_tables(W, W, dev), A._device_tables(H - abs(dy), H, dev)
+
+    def resample_steps(first=True):
+        stream = torch.cuda.current_stream().cuda_stream
+        if first:
+            steps[0].copy_(img)
+        for k in range(1, T):
+            A._launch(_augment_lib, steps[k - 1:k], 1, H, W, False, False, tx, ty, H, W, out_u8=steps[k:k + 1],
+                      stream=stream)
+
+    resample_steps()
+    if not torch.equal(steps, S.shift_chain(img, T, -dx, dy)):
+        raise SystemExit("the T - 1 resample launches and the chain disagree")
+    res = {"clip": f"{T}x{H}x{W}x3 u8 from one image", "dx": dx, "dy": dy, "launches": launches,
+           "device": torch.cuda.get_device_name(0), "out_bytes": out.numel()}
+    res["strip"], res["lds_bytes"] = _static_clip_lib.launch_plan(H, W)
+    timed = {"chain": lambda: S.shift_chain(img, T, dx, dy, out=out),
+             "chain_dx_pos": lambda: S.shift_chain(img, T, -dx, dy, out=out),
+             "copy": lambda: dst.copy_(out),
+             "steps": resample_steps,
+             "steps_without_frame0": lambda: resample_steps(False)}
+    for name, fn in timed.items():
+        t = event_times_ms(fn, 10, launches, big.zero_)
+        res[name + "_us_median"], res[name + "_us_min"] = statistics.median(t) * 1e3, t[0] * 1e3
+        res[name + "_us_p90"] = t[int(0.9 * len(t))] * 1e3
+    res["chain_over_copy"] = res["chain_us_median"] / res["copy_us_median"]
+    res["steps_over_chain"] = res["steps_us_median"] / res["chain_dx_pos_us_median"]
+    return res
+
+
 def host_steps(repeats, threads):
     from memotr_amd.data.augment import augment_clip
     frames, infos = clip()
@@ -127,10 +176,21 @@ def main():
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--threads", type=int, default=2)
     ap.add_argument("--step-timeout", type=int, default=240)
-    ap.add_argument("--gpu-step", choices=["plain", "crop"], help="(internal) run one GPU step in this process")
+    ap.add_argument("--static", action="store_true", help="the clip made from one still image, nothing else")
+    ap.add_argument("--gpu-step", choices=["plain", "crop", "static"],
+                    help="(internal) run one GPU step in this process")
     args = ap.parse_args()
     if args.gpu_step:
-        print(json.dumps(gpu_step(args.gpu_step, args.launches)))
+        step = static_step(args.launches) if args.gpu_step == "static" else gpu_step(args.gpu_step, args.launches)
+        print(json.dumps(step))
+        return
+    if args.static:
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpu-step", "static", "--launches", str(args.launches)]
+        done = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=args.step_timeout)
+        if done.returncode != 0:
+            sys.stderr.write(done.stderr)
+            raise SystemExit(f"GPU step static failed ({done.returncode})")
+        print(done.stdout.strip().splitlines()[-1])
         return
     result = {"clip": f"{T}x{H}x{W}x3 u8"}
     for name in ("plain", "crop"):
