@@ -16,7 +16,7 @@ The HIP library is mandatory: importing the operator without a built
 import os as _os
 
 # hipGraph replays on ROCm 7.2 mis-order memset nodes unless the runtime's AQL-packet capture is off (see
-# models/decoder_graphs.py, tools/graph_memset_probe.py).  The runtime reads the flag when it loads, i.e. this only
+# models/graph_capture.py, tools/graph_memset_probe.py).  The runtime reads the flag when it loads, i.e. this only
 # helps when the package is imported before torch; bench.py / the tests / __graft_entry__ set it themselves.  The
 # captured regions of this package contain no memset nodes either way (held by the GPU tests).
 _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")

@@ -11,21 +11,22 @@ What is captured: ``QueryUpdater.update_fields`` on ONE packed tensor [logits | 
 long_memory | last_output | query_embed] of the active tracks, rows padded with zeros to a multiple of ``BUCKET``
 (padded rows are excluded from the memory attention as keys -- the only place rows meet -- and are sliced away after the
 call, so they receive and produce zero gradient), returning the packed [ref_pts | long_memory | last_output |
-query_embed].  Parameters enter as one flat tensor made once per clip, as in models/decoder_graphs.py: the frames'
+query_embed].  Parameters enter as one flat tensor made once per clip (models/graph_capture.py): the frames'
 parameter gradients meet in one add per frame and DistributedDataParallel's hooks fire once per parameter.
 Anything that cannot be captured (CPU tensors, autocast, dropout in training mode, a capture error) runs eagerly.
 """
 from __future__ import annotations
 
 import os
+from typing import Callable, NamedTuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ..functions import clip_ops
-from .decoder_graphs import checked_capture
 from .graph_cache import GraphCache
+from .graph_capture import CapturedPair, FlatParameters, capture_pair
 
 BUCKET = 16
 # (frame slots x clips of the batch x row buckets) kept alive; least recently used go first -- small graphs (a few MB each);
@@ -52,12 +53,18 @@ class UpdateStep(nn.Module):
         return torch.cat(self.updater.update_fields(*fields, key_mask=key_mask), dim=1)
 
 
+class UpdaterEntry(NamedTuple):
+    pair: CapturedPair           # fn(packed, key_mask, flat parameters)
+    mask_for: Callable           # live row count -> the (1, rows) key mask of the padded slots
+
+
 class UpdaterGraphs(GraphCache):
     """Cache of captured embedding updates, owned by a ``QueryUpdater``."""
 
     def __init__(self, updater):
         super().__init__("query updater", MAX_GRAPHS, grow_cap=4)
         self.updater = updater
+        self._flat = {}          # the flat parameters of the current clip, shared by all captures
 
     def usable(self, fields) -> bool:
         u = self.updater
@@ -77,7 +84,6 @@ class UpdaterGraphs(GraphCache):
         entry = self.lookup(key, lambda: self._capture(rows, widths, fields[0].device))
         if entry is None:
             return None
-        fn, params, mask_for = entry
         if packed is not None and packed.shape[0] == n and packed.shape[1] >= sum(widths):
             packed = packed[:, :sum(widths)]
         else:
@@ -85,46 +91,20 @@ class UpdaterGraphs(GraphCache):
         if rows > n:
             packed = F.pad(packed, (0, 0, 0, rows - n))
         self.replays += 1
-        out = fn(packed, mask_for(n), self._flat_parameters(params, clip_key))
+        out = entry.pair.fn(packed, entry.mask_for(n), entry.pair.params.flat(clip_key))
         C = self.updater.hidden_dim
         return out[:n].split([4, C, C, out.shape[1] - 4 - 2 * C], dim=1)
 
-    def _flat_parameters(self, params, clip_key):
-        cache = self.__dict__.get("_flat")
-        if (clip_key is not None and cache is not None and cache[0] is clip_key and len(cache[1]) == len(params)
-                and all(a is b for a, b in zip(cache[1], params))):
-            return cache[2]
-        flat = torch.cat([p.reshape(-1) for p in params])
-        self.__dict__["_flat"] = (clip_key, params, flat)
-        return flat
-
     def _capture(self, rows, widths, device):
         step = UpdateStep(self.updater, widths)
-        names, params = zip(*step.named_parameters())
-        if len(names) != sum(1 for _ in step.named_parameters(remove_duplicate=False)):
-            self.failed = True
-            return None
-        sizes = [p.numel() for p in params]
-        views = [p.shape for p in params]
+        params = FlatParameters(step, step.named_parameters(), False, shared=self._flat)
 
         def run(packed, key_mask, flat):
-            pieces = flat.split(sizes)
-            return torch.func.functional_call(step, {n: w.view(s) for n, w, s in zip(names, pieces, views)},
-                                              (packed, key_mask))
+            return torch.func.functional_call(step, params.substitution(flat), (packed, key_mask))
 
-        with torch.no_grad():
-            flat = torch.cat([p.reshape(-1) for p in params])
         g = torch.Generator(device="cpu").manual_seed(0)
         sample = (torch.randn(rows, sum(widths), generator=g).to(device).requires_grad_(True),
-                  torch.zeros((1, rows), dtype=torch.bool, device=device), flat.requires_grad_(True))
-        try:
-            fn = checked_capture(lambda: torch.cuda.make_graphed_callables(run, sample, num_warmup_iters=2,
-                                                                           allow_unused_input=True))
-        except Exception as exc:  # noqa: BLE001 -- capture is an optimisation; eager stays valid
-            return self.capture_failed(exc)
-        assert all(isinstance(p, nn.Parameter) for p in step.parameters()) and \
-            [id(p) for p in step.parameters()] == [id(p) for p in params], "updater parameters were replaced"
-        self.captures += 1
+                  torch.zeros((1, rows), dtype=torch.bool, device=device))
         masks = {}
 
         def mask_for(n):           # (1, rows) bool, True on the padded slots; one tensor per live count, made once
@@ -133,4 +113,5 @@ class UpdaterGraphs(GraphCache):
                 m = masks[n] = (torch.arange(rows, device=device) >= n)[None]
             return m
 
-        return fn, params, mask_for
+        pair = capture_pair(self, params, run, sample)
+        return pair and UpdaterEntry(pair, mask_for)

@@ -206,7 +206,7 @@ class MSDeformAttn(nn.Module):
         pre = getattr(so.weight, "_msda_fused_qproj", None)
         if pre is not None:
             # a capture whose flat parameter argument holds the two weights (and the two biases) next to each other
-            # (models/decoder_graphs.py: paired_query_projections): the stack is a view, nothing to concatenate
+            # (models/graph_capture.py: paired_query_projections): the stack is a view, nothing to concatenate
             return pre
         if so.weight.is_cuda and torch.cuda.is_current_stream_capturing():
             # inside a hipGraph capture the concatenation must be part of the graph (a cached tensor would freeze the

@@ -52,7 +52,7 @@ def run_train(args, rank: int, world: int, clip_len: int = None, height: int = 8
     from .models.criterion import build as build_criterion
     from .utils.utils import set_seed
 
-    # a decoder-graph capture that fails is an error in the benchmark, not a silent eager run (models/decoder_graphs.py)
+    # a decoder-graph capture that fails is an error in the benchmark, not a silent eager run (models/graph_cache.py)
     os.environ.setdefault("MEMOTR_REQUIRE_GRAPHS", "1")
     clip_len = clip_len or int(os.environ.get("MEMOTR_BENCH_CLIP_LEN", "5"))
     cfg = config or dancetrack_config()

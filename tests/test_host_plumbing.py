@@ -297,15 +297,25 @@ def test_track_instances_row_gather_and_padded_stack():
     assert MeMOTR._pad_stack(_Stub(), [torch.zeros(0, 4)], 4).shape == (1, 0, 4)
 
 
-def test_decoder_graphs_flat_parameters_are_shared_within_a_clip_only():
-    from memotr_amd.models.decoder_graphs import DecoderGraphs
-    g = DecoderGraphs(decoder=None)
+def test_flat_parameters_are_shared_within_a_clip_only():
+    """models/graph_capture.py: every frame slot has a capture -- and a ``FlatParameters`` -- of its own; those of one
+    cache share the clip's flat tensor (same clip key object, same parameter objects), and nothing is kept without a key."""
+    from memotr_amd.models.graph_capture import FlatParameters
     params = (nn.Parameter(torch.randn(3, 2)), nn.Parameter(torch.randn(5)))
+    root = nn.ParameterList(params)
+    shared = {}
+    g = FlatParameters(root, root.named_parameters(), True, shared=shared)
     clip_a, clip_b = object(), object()
-    f1 = g._flat_parameters(params, clip_a)
+    f1 = g.flat(clip_a)
     assert f1.shape == (11,) and f1.requires_grad
-    assert g._flat_parameters(tuple(params), clip_a) is f1               # same clip, same parameters: the same tensor
-    assert g._flat_parameters(params, clip_b) is not f1                   # a new clip re-reads the parameters
-    assert g._flat_parameters(params, None) is not g._flat_parameters(params, None)   # no key: never cached
+    assert g.flat(clip_a) is f1                                            # same clip, same parameters: the same tensor
+    other_slot = FlatParameters(root, root.named_parameters(), True, shared=shared)
+    assert other_slot.params is not g.params and other_slot.flat(clip_a) is f1     # ... also for another slot's capture
+    assert FlatParameters(root, root.named_parameters(), True).flat(clip_a) is not f1    # ... but not for another cache's
+    f2 = g.flat(clip_b)
+    assert f2 is not f1 and g.flat(clip_b) is f2                           # a new clip re-reads the parameters
+    root[1] = nn.Parameter(torch.zeros(5))                                 # a replaced parameter: not the cached tensor
+    assert FlatParameters(root, root.named_parameters(), True, shared=shared).flat(clip_b) is not f2
+    assert g.flat(None) is not g.flat(None) and g.flat() is not g.flat()   # no key: never cached
     f1.sum().backward()
     assert torch.equal(params[0].grad, torch.ones(3, 2))

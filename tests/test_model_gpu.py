@@ -413,7 +413,7 @@ def test_decoder_graphs_are_captured_and_match_the_eager_loop(monkeypatch):
 def test_memset_nodes_are_ordered_on_replay_in_the_test_environment():
     """conftest.py sets DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 before torch loads the HIP runtime: with it a memset node of a
     replayed graph runs where it was captured (kernel | memset | kernel probe); without it ROCm 7.2 runs it first."""
-    from memotr_amd.models import decoder_graphs as dg
+    from memotr_amd.models import graph_capture as dg
     assert os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
     assert dg.memset_nodes_replay_safe()
 
@@ -421,7 +421,7 @@ def test_memset_nodes_are_ordered_on_replay_in_the_test_environment():
 def test_a_capture_holding_memset_nodes_is_refused_when_the_runtime_misorders_them(monkeypatch):
     """On a runtime that fails the probe every captured graph is inspected, and one with a memset node (a library
     zeroing a workspace) is an error under MEMOTR_REQUIRE_GRAPHS=1 and an eager fallback otherwise -- never replayed."""
-    from memotr_amd.models import decoder_graphs as dg
+    from memotr_amd.models import graph_capture as dg
     monkeypatch.setattr(dg, "_MEMSET_SAFE", False)
     monkeypatch.setattr(dg, "graph_node_census", lambda g: {"kernel": 7, "memset": 1})
     with pytest.raises(RuntimeError, match="DEBUG_CLR_GRAPH_PACKET_CAPTURE"):
@@ -447,23 +447,29 @@ def test_decoder_graph_key_is_the_geometry_not_the_tensor_object(monkeypatch):
 
 def test_decoder_graph_cache_stops_capturing_when_every_clip_has_a_new_geometry(monkeypatch):
     from memotr_amd.models import decoder_graphs as dg
+    from memotr_amd.models.graph_cache import MISS_LIMIT, RETRY_AFTER
+    from memotr_amd.models.graph_capture import CapturedPair
 
     class _Dec:       # stands in for the decoder: only the capture counter matters here
         pass
 
+    class _Params:    # ... and for the flat parameters of a capture
+        def flat(self, clip_key=None):
+            return None
+
     cache = dg.DecoderGraphs(_Dec())
     calls = []
-    monkeypatch.setattr(cache, "_capture", lambda args, shapes, lsi: calls.append(1) or (lambda *a: "ran", ()))
-    monkeypatch.setattr(cache, "_flat_parameters", lambda params, clip_key: None)
+    monkeypatch.setattr(cache, "_capture",
+                        lambda args, shapes, lsi: calls.append(1) or CapturedPair(lambda *a: "ran", _Params()))
     monkeypatch.setattr(dg.DecoderGraphs, "_geometry", staticmethod(lambda s: s))
     x = (torch.zeros(1),)
-    for i in range(dg.MISS_LIMIT + 5):          # a new geometry every time
+    for i in range(MISS_LIMIT + 5):          # a new geometry every time
         cache.run(0, x, ("geo", i), None)
-    assert len(calls) == dg.MISS_LIMIT and cache.eager == 5
+    assert len(calls) == MISS_LIMIT and cache.eager == 5
     assert cache.run(0, x, ("geo", 0), None) == "ran"       # what was captured still replays
-    for i in range(dg.RETRY_AFTER):
+    for i in range(RETRY_AFTER):
         cache.run(0, x, ("other", i), None)
-    assert len(calls) > dg.MISS_LIMIT                         # ... and the cache re-arms after RETRY_AFTER eager calls
+    assert len(calls) > MISS_LIMIT                         # ... and the cache re-arms after RETRY_AFTER eager calls
 
 
 def test_track_augmentation_masks_built_on_the_cpu_index_cuda_tracks(monkeypatch):
@@ -588,13 +594,13 @@ def test_encode_graphs_match_the_eager_encode(monkeypatch, bf16):
         grads = {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None}
         return float(loss), grads, model.encode_graphs()
 
-    from memotr_amd.models import decoder_graphs
+    from memotr_amd.models import graph_capture
     loss_e, g_e, cache_e = run(False)
     assert cache_e.captures == 0 and cache_e.replays == 0
     census = []
-    monkeypatch.setattr(decoder_graphs, "CENSUS", census)
+    monkeypatch.setattr(graph_capture, "CENSUS", census)
     loss_g, g_g, cache = run(True, steps=3)                 # steps 2 and 3 replay the first step's capture
-    monkeypatch.setattr(decoder_graphs, "CENSUS", None)
+    monkeypatch.setattr(graph_capture, "CENSUS", None)
     assert cache.captures == 1 and cache.replays == 3 and cache.eager == 0 and not cache.failed
     # no memset node in any captured graph (encode pair + decoder pairs): on ROCm 7.2 such a node is not ordered
     # behind the kernels before it when the graph is replayed (tools/graph_memset_probe.py)
@@ -603,7 +609,7 @@ def test_encode_graphs_match_the_eager_encode(monkeypatch, bf16):
     # the entry keeps what the capture read through raw pointers alive (the clip's padding masks among them: the
     # engine builds a new NestedTensor every step, and replay 1 once read a recycled one)
     (entry,) = cache.slots.values()
-    assert any(torch.is_tensor(p) and p.dtype == torch.bool and p.dim() == 3 for p in entry[4])
+    assert any(torch.is_tensor(p) and p.dtype == torch.bool and p.dim() == 3 for p in entry.pins)
     tol_loss, tol_grad = (2e-2, 0.2) if bf16 else (2e-4, 2e-2)
     assert abs(loss_g - loss_e) <= tol_loss * abs(loss_e), (loss_g, loss_e)
     assert g_g.keys() == g_e.keys()
@@ -656,6 +662,11 @@ def test_inference_graphs_match_the_eager_tracker(monkeypatch):
     assert 1 <= dec.captures <= 3 and dec.replays >= len(frames) and dec.eager == 0 and not dec.failed
     assert len(eager[-1]) >= 3
     assert model_a.infer_graphs().encode.captures == 2          # two slots: one may still be read by the decoder
+    # each encode entry keeps what its capture read through raw pointers alive, the frame's padding mask among them (as
+    # the training encode entry does), and carries the mask-derived constants from the moment it was captured
+    for entry in enc.slots.values():
+        assert any(torch.is_tensor(p) and p.dtype == torch.bool and p.dim() == 3 for p in entry.pins)
+        assert entry.constants and "memory" not in entry.constants
     for other in (graphed, ahead_eager, ahead):
         for a, b in zip(eager, other):
             assert a.ids.tolist() == b.ids.tolist()

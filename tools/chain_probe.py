@@ -64,6 +64,7 @@ if "--fine" in sys.argv:        # one level further down
     from memotr_amd.functions import clip_ops as _co  # noqa: E402
     from memotr_amd.models import criterion as _cr  # noqa: E402
     from memotr_amd.models.decoder_graphs import DecoderGraphs  # noqa: E402
+    from memotr_amd.models.graph_capture import FlatParameters  # noqa: E402
     from memotr_amd.models.deformable_decoder import DeformableDecoder  # noqa: E402
     from memotr_amd.models.deformable_transformer import DeformableTransformer  # noqa: E402
     from memotr_amd.models.updater_graphs import UpdaterGraphs  # noqa: E402
@@ -73,7 +74,7 @@ if "--fine" in sys.argv:        # one level further down
     wrap(DeformableTransformer, "decode")
     wrap(DeformableDecoder, "_forward_graphed")
     wrap(DecoderGraphs, "run", "DecoderGraphs.run")
-    wrap(DecoderGraphs, "_flat_parameters")
+    wrap(FlatParameters, "flat", "_flat_parameters")
     wrap(UpdaterGraphs, "run", "UpdaterGraphs.run")
     wrap(ClipCriterion, "update_tracked_instances")
     wrap(_cr, "upload")

@@ -3,7 +3,7 @@
     python tools/graph_census.py [--dtype bf16] [--small]
 
 Why it exists: a memset node inside a captured region is a replay hazard on ROCm 7.2 (tools/graph_memset_probe.py,
-models/decoder_graphs.py) -- the captured regions of this package are held to zero of them."""
+models/graph_capture.py) -- the captured regions of this package are held to zero of them."""
 import argparse
 import os
 import sys
@@ -26,11 +26,11 @@ def main():
     args = ap.parse_args()
     os.environ["MEMOTR_ENCODE_GRAPHS"] = args.encode_graphs
     from memotr_amd import train_bench
-    from memotr_amd.models import decoder_graphs
+    from memotr_amd.models import graph_capture
     res = train_bench.run_train(args, 0, 1, dtype=args.dtype)
     print({k: res[k] for k in ("value", "ms_per_step", "decoder_graph_stats")})
     total = {}
-    for i, c in enumerate(decoder_graphs.CENSUS):
+    for i, c in enumerate(graph_capture.CENSUS):
         print(f"capture {i:3d}: {c}")
         for k, v in c.items():
             total[k] = total.get(k, 0) + v

@@ -12,7 +12,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import memotr_amd  # noqa: F401,E402  (sets DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 unless the caller chose)
 import torch  # noqa: E402
-from memotr_amd.models.decoder_graphs import graph_node_census  # noqa: E402
+from memotr_amd.models.graph_capture import graph_node_census  # noqa: E402
 
 
 def build(n_kernels, n_copies, big_copy=False):

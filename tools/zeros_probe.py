@@ -2,7 +2,7 @@ import os, sys, time
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 sys.path.insert(0, "/root/repo")
 import torch
-from memotr_amd.models import decoder_graphs as dg
+from memotr_amd.models import graph_capture as dg
 dev = torch.device("cuda")
 for shape in [(1, 22323, 6, 8, 32), (1, 22323, 8, 32), (6,), (1, 1000, 6, 8, 32)]:
     census = []
