@@ -1,6 +1,7 @@
 """Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
-step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation) and
-libstatic_clip_ops_hip.so (clips made from one still image) with hipcc for gfx950 (cross-compiles without a GPU)."""
+step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation),
+libstatic_clip_ops_hip.so (clips made from one still image) and libtrack_eval_hip.so (HOTA / CLEAR / Identity
+evaluation) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -30,6 +31,9 @@ AUGMENT_LIB = os.path.join(LIB_DIR, "libaugment_ops_hip.so")
 STATIC_CLIP_SRC = os.path.join(_HERE, "csrc", "static_clip_ops.hip")
 STATIC_CLIP_HDR = os.path.join(os.path.dirname(_HERE), "include", "static_clip_ops_hip.h")
 STATIC_CLIP_LIB = os.path.join(LIB_DIR, "libstatic_clip_ops_hip.so")
+TRACK_EVAL_SRC = os.path.join(_HERE, "csrc", "track_eval.hip")
+TRACK_EVAL_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_eval_hip.h")
+TRACK_EVAL_LIB = os.path.join(LIB_DIR, "libtrack_eval_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -66,9 +70,9 @@ def needs_build() -> bool:
     return _stale(LIB, (SRC, HDR) + KERNEL_HEADERS)
 
 
-def _compile(src: str, lib: str, verbose: bool) -> str:
+def _compile(src: str, lib: str, verbose: bool, extra=()) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc_path(), *HIPCC_FLAGS, src, "-o", lib]
+    cmd = [hipcc_path(), *HIPCC_FLAGS, *extra, src, "-o", lib]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -105,9 +109,17 @@ def build_static_clip_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(STATIC_CLIP_SRC, STATIC_CLIP_LIB, verbose)
 
 
+def build_track_eval_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(TRACK_EVAL_LIB, (TRACK_EVAL_SRC, TRACK_EVAL_HDR, ASSIGN_CORE)):
+        return TRACK_EVAL_LIB
+    # float64 results are held to TrackEval's bit for bit where the definition allows it: no fused multiply-add
+    return _compile(TRACK_EVAL_SRC, TRACK_EVAL_LIB, verbose, extra=("-ffp-contract=off",))
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
     print(build_frame_lib(force=True, verbose=True))
     print(build_augment_lib(force=True, verbose=True))
     print(build_static_clip_lib(force=True, verbose=True))
+    print(build_track_eval_lib(force=True, verbose=True))

@@ -131,9 +131,18 @@ struct SerialLanes {
     ASSIGN_HD void sync() const {}
 };
 
-// Solve one problem with nr <= nc.  Returns false when no complete assignment exists (an infinite column set).
-template <typename Lanes>
-ASSIGN_HD bool solve_rows_le_cols(const Lanes &lanes, const CostView &cost, int nr, int nc, const Work &w) {
+// Any cost view seen through its transpose: how a "tall" problem is handed to the solver below.
+template <typename View>
+struct Transposed {
+    View v;
+    ASSIGN_HD double at(int i, int j) const { return v.at(j, i); }
+};
+
+// Solve one problem with nr <= nc.  `Cost` is anything with `double at(i, j) const`: a matrix in memory (CostView) or
+// a function of other data (track_eval.hip: scores and counts that are never materialised as a matrix).  Returns false
+// when no complete assignment exists (an infinite column set).
+template <typename Lanes, typename Cost>
+ASSIGN_HD bool solve_rows_le_cols(const Lanes &lanes, const Cost &cost, int nr, int nc, const Work &w) {
     lanes.each(nr, [&](int i) { w.u[i] = 0.0; w.col4row[i] = -1; });
     lanes.each(nc, [&](int j) { w.v[j] = 0.0; w.row4col[j] = -1; w.path[j] = -1; });
     lanes.sync();
@@ -203,18 +212,10 @@ ASSIGN_HD bool solve_rows_le_cols(const Lanes &lanes, const CostView &cost, int 
     return true;
 }
 
-// One (n_rows x n_cols) problem, cost row-major with the given strides: min(n_rows, n_cols) pairs, ordered by row
-// index like scipy's result (`row_ind` ascending).  `mem` holds work_bytes(min, max) bytes.  Returns the number of
-// pairs, or -1 for an infeasible matrix.
+// The pairs of a solved problem (w of solve_rows_le_cols) in scipy's order, `row_ind` ascending; lane 0 writes them.
 template <typename Lanes>
-ASSIGN_HD int solve_problem(const Lanes &lanes, const float *cost, long stride_row, long stride_col, int n_rows,
-                            int n_cols, void *mem, int32_t *row_ind, int32_t *col_ind) {
-    if (n_rows <= 0 || n_cols <= 0) return 0;
-    const bool transposed = n_cols < n_rows;             // scipy: "tall" problems are solved on the transpose
-    const int nr = transposed ? n_cols : n_rows, nc = transposed ? n_rows : n_cols;
-    const CostView view{cost, transposed ? stride_col : stride_row, transposed ? stride_row : stride_col};
-    const Work w = carve(mem, nr, nc);
-    if (!solve_rows_le_cols(lanes, view, nr, nc, w)) return -1;
+ASSIGN_HD void write_pairs(const Lanes &lanes, const Work &w, bool transposed, int nr, int nc, int32_t *row_ind,
+                           int32_t *col_ind) {
     if (lanes.leader()) {
         if (!transposed) {
             for (int i = 0; i < nr; ++i) {
@@ -232,7 +233,63 @@ ASSIGN_HD int solve_problem(const Lanes &lanes, const float *cost, long stride_r
         }
     }
     lanes.sync();
+}
+
+// One (n_rows x n_cols) problem whose cost is `view.at(row, col)`: min(n_rows, n_cols) pairs ordered by row index,
+// into row_ind / col_ind (any memory all lanes see: LDS or global).  `mem` holds work_bytes(min, max) bytes.  Returns
+// the number of pairs, or -1 for an infeasible problem.  Problems of one launch may differ in shape: the caller sizes
+// `mem` for the largest.
+template <typename Lanes, typename View>
+ASSIGN_HD int solve_view(const Lanes &lanes, const View &view, int n_rows, int n_cols, void *mem, int32_t *row_ind,
+                         int32_t *col_ind) {
+    if (n_rows <= 0 || n_cols <= 0) return 0;
+    const bool transposed = n_cols < n_rows;             // scipy: "tall" problems are solved on the transpose
+    const int nr = transposed ? n_cols : n_rows, nc = transposed ? n_rows : n_cols;
+    const Work w = carve(mem, nr, nc);
+    const bool ok = transposed ? solve_rows_le_cols(lanes, Transposed<View>{view}, nr, nc, w)
+                               : solve_rows_le_cols(lanes, view, nr, nc, w);
+    if (!ok) return -1;
+    write_pairs(lanes, w, transposed, nr, nc, row_ind, col_ind);
     return nr;
 }
+
+// One (n_rows x n_cols) problem, cost row-major with the given strides: min(n_rows, n_cols) pairs, ordered by row
+// index like scipy's result (`row_ind` ascending).  `mem` holds work_bytes(min, max) bytes.  Returns the number of
+// pairs, or -1 for an infeasible matrix.
+template <typename Lanes>
+ASSIGN_HD int solve_problem(const Lanes &lanes, const float *cost, long stride_row, long stride_col, int n_rows,
+                            int n_cols, void *mem, int32_t *row_ind, int32_t *col_ind) {
+    return solve_view(lanes, CostView{cost, stride_row, stride_col}, n_rows, n_cols, mem, row_ind, col_ind);
+}
+
+#if defined(__HIPCC__)
+// The wavefront's side of Lanes: lane l scans positions l, l + 64, ... of the unvisited-column list and the 64 partial
+// results meet in an xor butterfly of the (commutative, associative) merge; everything that is not the scan is
+// wave-uniform control flow around LDS arrays, with a workgroup barrier (one wavefront: an s_barrier and the LDS wait)
+// wherever one lane's LDS write must be seen by the others.  For kernels launched with 64 threads per workgroup.
+struct WaveLanes {
+    int lane;
+    template <typename F>
+    __device__ __forceinline__ ScanBest scan(int n, F &&body) const {
+        ScanBest mine = scan_empty();
+        for (int it = lane; it < n; it += 64) body(it, mine);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            ScanBest o;
+            o.lowest = __shfl_xor(mine.lowest, off, 64);
+            o.last_free = __shfl_xor(mine.last_free, off, 64);
+            o.first = __shfl_xor(mine.first, off, 64);
+            mine = scan_merge(mine, o);
+        }
+        return mine;
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(int n, F &&body) const {
+        for (int k = lane; k < n; k += 64) body(k);
+    }
+    __device__ __forceinline__ bool leader() const { return lane == 0; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+#endif
 
 }  // namespace assign

@@ -815,33 +815,8 @@ __global__ __launch_bounds__(256) void add_layer_norm_bwd_kernel(const float *__
 }
 
 // ---- linear sum assignment on the device (assign_core.h; one wavefront per problem) ----------------------------
-// The wavefront's side of assign::Lanes: lane l scans positions l, l + 64, ... of the unvisited-column list and the
-// 64 partial results meet in an xor butterfly of the (commutative, associative) merge; everything that is not the scan
-// is wave-uniform control flow around LDS arrays, with a workgroup barrier (one wavefront: an s_barrier and the LDS
-// wait) wherever one lane's LDS write must be seen by the others.
-struct WaveLanes {
-    int lane;
-    template <typename F>
-    __device__ __forceinline__ assign::ScanBest scan(int n, F &&body) const {
-        assign::ScanBest mine = assign::scan_empty();
-        for (int it = lane; it < n; it += 64) body(it, mine);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            assign::ScanBest o;
-            o.lowest = __shfl_xor(mine.lowest, off, 64);
-            o.last_free = __shfl_xor(mine.last_free, off, 64);
-            o.first = __shfl_xor(mine.first, off, 64);
-            mine = assign::scan_merge(mine, o);
-        }
-        return mine;
-    }
-    template <typename F>
-    __device__ __forceinline__ void each(int n, F &&body) const {
-        for (int k = lane; k < n; k += 64) body(k);
-    }
-    __device__ __forceinline__ bool leader() const { return lane == 0; }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
+// (assign::WaveLanes, the wavefront's side of the solver, lives with it in assign_core.h)
+using assign::WaveLanes;
 
 __global__ __launch_bounds__(64) void assign_kernel(const float *__restrict__ cost, long stride_p, long stride_r,
                                                     long stride_c, int n_rows, int n_cols,
