@@ -1,7 +1,8 @@
 """Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
 step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation),
-libstatic_clip_ops_hip.so (clips made from one still image) and libtrack_eval_hip.so (HOTA / CLEAR / Identity
-evaluation) with hipcc for gfx950 (cross-compiles without a GPU)."""
+libstatic_clip_ops_hip.so (clips made from one still image), libtrack_eval_hip.so (HOTA / CLEAR / Identity
+evaluation) and libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) with hipcc for
+gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -34,6 +35,9 @@ STATIC_CLIP_LIB = os.path.join(LIB_DIR, "libstatic_clip_ops_hip.so")
 TRACK_EVAL_SRC = os.path.join(_HERE, "csrc", "track_eval.hip")
 TRACK_EVAL_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_eval_hip.h")
 TRACK_EVAL_LIB = os.path.join(LIB_DIR, "libtrack_eval_hip.so")
+TRACK_EVAL_BDD_SRC = os.path.join(_HERE, "csrc", "track_eval_bdd.hip")
+TRACK_EVAL_BDD_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_eval_bdd_hip.h")
+TRACK_EVAL_BDD_LIB = os.path.join(LIB_DIR, "libtrack_eval_bdd_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -116,6 +120,14 @@ def build_track_eval_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(TRACK_EVAL_SRC, TRACK_EVAL_LIB, verbose, extra=("-ffp-contract=off",))
 
 
+def build_track_eval_bdd_lib(force: bool = False, verbose: bool = False) -> str:
+    deps = (TRACK_EVAL_BDD_SRC, TRACK_EVAL_BDD_HDR, TRACK_EVAL_HDR, ASSIGN_CORE)
+    if not force and not _stale(TRACK_EVAL_BDD_LIB, deps):
+        return TRACK_EVAL_BDD_LIB
+    # the same arithmetic rules as libtrack_eval_hip.so: similarities are TrackEval's bit for bit
+    return _compile(TRACK_EVAL_BDD_SRC, TRACK_EVAL_BDD_LIB, verbose, extra=("-ffp-contract=off",))
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
@@ -123,3 +135,4 @@ if __name__ == "__main__":
     print(build_augment_lib(force=True, verbose=True))
     print(build_static_clip_lib(force=True, verbose=True))
     print(build_track_eval_lib(force=True, verbose=True))
+    print(build_track_eval_bdd_lib(force=True, verbose=True))
