@@ -1,8 +1,9 @@
 """Build memotr_amd/lib/libmsda_hip.so (the operator), libclip_ops_hip.so (fused small-tensor chains of the train
 step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation),
 libstatic_clip_ops_hip.so (clips made from one still image), libtrack_eval_hip.so (HOTA / CLEAR / Identity
-evaluation) and libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) with hipcc for
-gfx950 (cross-compiles without a GPU)."""
+evaluation), libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) and
+libtrack_motion_hip.so (the online tracker's motion post-process) with hipcc for gfx950 (cross-compiles without a
+GPU)."""
 from __future__ import annotations
 
 import os
@@ -38,6 +39,9 @@ TRACK_EVAL_LIB = os.path.join(LIB_DIR, "libtrack_eval_hip.so")
 TRACK_EVAL_BDD_SRC = os.path.join(_HERE, "csrc", "track_eval_bdd.hip")
 TRACK_EVAL_BDD_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_eval_bdd_hip.h")
 TRACK_EVAL_BDD_LIB = os.path.join(LIB_DIR, "libtrack_eval_bdd_hip.so")
+TRACK_MOTION_SRC = os.path.join(_HERE, "csrc", "track_motion.hip")
+TRACK_MOTION_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_motion_hip.h")
+TRACK_MOTION_LIB = os.path.join(LIB_DIR, "libtrack_motion_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -128,6 +132,13 @@ def build_track_eval_bdd_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(TRACK_EVAL_BDD_SRC, TRACK_EVAL_BDD_LIB, verbose, extra=("-ffp-contract=off",))
 
 
+def build_track_motion_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(TRACK_MOTION_LIB, (TRACK_MOTION_SRC, TRACK_MOTION_HDR)):
+        return TRACK_MOTION_LIB
+    # float32 add, mul and div are the host statement's bit for bit (models/motion.py): no fused multiply-add
+    return _compile(TRACK_MOTION_SRC, TRACK_MOTION_LIB, verbose, extra=("-ffp-contract=off",))
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
@@ -136,3 +147,4 @@ if __name__ == "__main__":
     print(build_static_clip_lib(force=True, verbose=True))
     print(build_track_eval_lib(force=True, verbose=True))
     print(build_track_eval_bdd_lib(force=True, verbose=True))
+    print(build_track_motion_lib(force=True, verbose=True))

@@ -26,6 +26,7 @@ def dancetrack_config(**overrides) -> dict:
         LOSS_WEIGHT_GIOU=2, AUX_LOSS_WEIGHT=[1.0, 1.0, 1.0, 1.0, 1.0],
         # inference thresholds (:24-33)
         DET_SCORE_THRESH=0.5, TRACK_SCORE_THRESH=0.5, RESULT_SCORE_THRESH=0.5, MISS_TOLERANCE=30, USE_MOTION=False,
+        MOTION_MIN_LENGTH=3, MOTION_MAX_LENGTH=5, MOTION_LAMBDA=0.5,
     )
     cfg.update(overrides)
     return cfg

@@ -18,6 +18,9 @@ From decoded frames (uint8, H x W x 3, e.g. what ``cv2.imread`` returns) instead
 
 ``track`` is ``step_raw(frame, next_frame)`` in a loop: upload through pinned memory, one kernel (data/frames.py),
 then the same encode / decode path as ``step``.
+
+``use_motion=True`` (the reference's ``USE_MOTION``): after the query updater, the reference point of every track that
+is being missed is moved along its mean box velocity (models/motion.py: device state, one launch, no synchronisation).
 """
 from __future__ import annotations
 
@@ -40,7 +43,8 @@ MOT_STYLE = ("DanceTrack", "SportsMOT", "MOT17", "MOT17_SPLIT")
 class SequenceTracker:
     def __init__(self, model, dataset_name: str = "DanceTrack", det_score_thresh: float = 0.7,
                  track_score_thresh: float = 0.6, result_score_thresh: float = 0.7, miss_tolerance: int = 5,
-                 use_dab: bool = True, area_thresh: int = 100, raw_size=(800, 1536)):
+                 use_dab: bool = True, area_thresh: int = 100, raw_size=(800, 1536), use_motion: bool = False,
+                 motion_lambda: float = 0.5, motion_min_length: int = 3, motion_max_length: int = 5):
         from .utils.host import respect_cpu_quota
         respect_cpu_quota()           # (a container's CFS quota vs torch's machine-sized thread pool: utils/host.py)
         self.model = model.eval()
@@ -51,7 +55,10 @@ class SequenceTracker:
         self.use_dab = use_dab
         self.device = next(self.core.parameters()).device
         self.tracker = RuntimeTracker(det_score_thresh=det_score_thresh, track_score_thresh=track_score_thresh,
-                                      miss_tolerance=miss_tolerance, use_dab=use_dab)
+                                      miss_tolerance=miss_tolerance, use_dab=use_dab, use_motion=use_motion,
+                                      motion_min_length=motion_min_length, motion_max_length=motion_max_length)
+        self.use_motion = use_motion  # the reference's USE_MOTION post-process (models/motion.py); off in its configs
+        self.motion_lambda = motion_lambda
         self.tracks: List[TrackInstances] = [TrackInstances(hidden_dim=self.core.hidden_dim,
                                                             num_classes=self.core.num_classes,
                                                             use_dab=use_dab).to(self.device)]
@@ -66,7 +73,10 @@ class SequenceTracker:
     def from_config(cls, model, config: dict) -> "SequenceTracker":
         return cls(model, dataset_name=config["DATASET"], det_score_thresh=config["DET_SCORE_THRESH"],
                    track_score_thresh=config["TRACK_SCORE_THRESH"], result_score_thresh=config["RESULT_SCORE_THRESH"],
-                   miss_tolerance=config["MISS_TOLERANCE"], use_dab=config["USE_DAB"])
+                   miss_tolerance=config["MISS_TOLERANCE"], use_dab=config["USE_DAB"],
+                   use_motion=config.get("USE_MOTION", False), motion_lambda=config.get("MOTION_LAMBDA", 0.5),
+                   motion_min_length=config.get("MOTION_MIN_LENGTH", 3),
+                   motion_max_length=config.get("MOTION_MAX_LENGTH", 5))
 
     @torch.no_grad()
     def step(self, image: torch.Tensor, ori_h: int, ori_w: int, next_image: torch.Tensor = None) -> TrackInstances:
@@ -79,7 +89,17 @@ class SequenceTracker:
             self._prefetch(next_image)
         previous, new = self.tracker.update(model_outputs=res, tracks=self.tracks)
         self.tracks = self.core.postprocess_single_frame(previous, new, None)
+        if self.use_motion:
+            self._extrapolate_missed()
         return self._report(self.tracks[0], ori_h, ori_w)
+
+    def _extrapolate_missed(self) -> None:
+        """submit_engine.py:78-87: the reference point of a track that is being missed moves along its mean box
+        velocity -- one launch, and a NEW ref_pts tensor (the updater's captured graphs may own the old one)."""
+        t = self.tracks[0]
+        if len(t) > 0:
+            t.ref_pts = self.tracker.motions.extrapolate(t.ids, t.disappear_time, t.last_appear_boxes, t.ref_pts,
+                                                         self.motion_lambda)
 
     def _report(self, t: TrackInstances, ori_h: int, ori_w: int) -> TrackInstances:
         """The reportable tracks on the CPU (submit_engine.py:95-112): score and area filters, xyxy pixel boxes.
@@ -165,6 +185,8 @@ class SequenceTracker:
             self._prefetch_raw(next_frame_u8, bgr)
         previous, new = self.tracker.update(model_outputs=res, tracks=self.tracks)
         self.tracks = self.core.postprocess_single_frame(previous, new, None)
+        if self.use_motion:
+            self._extrapolate_missed()
         return self._report(self.tracks[0], ori_h, ori_w)
 
     def track(self, frames, *, bgr: bool = False):

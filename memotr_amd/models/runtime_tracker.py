@@ -2,7 +2,8 @@
 
 Same thresholds, id assignment and TrackInstances fields as the reference; the per-track python loop
 with ``.item()`` reads (runtime_tracker.py:43-54) is replaced by tensor ops on the device.
-The optional motion post-process (``USE_MOTION``, off in every shipped config) is not implemented.
+The optional motion post-process (``USE_MOTION``, off in every shipped config) keeps its per-track box history in a
+device table (models/motion.py): one launch for the existing tracks, one for the newborn, no extra synchronisation.
 """
 from __future__ import annotations
 
@@ -18,13 +19,17 @@ class RuntimeTracker:
     def __init__(self, det_score_thresh: float = 0.7, track_score_thresh: float = 0.6, miss_tolerance: int = 5,
                  use_motion: bool = False, motion_min_length: int = 3, motion_max_length: int = 5,
                  visualize: bool = False, use_dab: bool = True):
-        if use_motion:
-            raise NotImplementedError("USE_MOTION is not supported (unused by the shipped configs)")
         self.det_score_thresh = det_score_thresh
         self.track_score_thresh = track_score_thresh
         self.miss_tolerance = miss_tolerance
         self.max_obj_id = 0
-        self.use_motion = False
+        self.use_motion = use_motion
+        self.motion_min_length = motion_min_length
+        self.motion_max_length = motion_max_length
+        self.motions = None           # MotionState (replaces the reference's Dict[int, Motion]): made by the first update
+        if use_motion:
+            from .motion import MotionState
+            MotionState(motion_max_length, motion_min_length, "cpu", capacity=1)     # (argument errors: raised here)
         self.visualize = visualize
         self.use_dab = use_dab
 
@@ -40,7 +45,15 @@ class RuntimeTracker:
         t.logits = model_outputs["pred_logits"][0][n_dets:]
         t.output_embed = model_outputs["outputs"][0][n_dets:]
         t.scores = logits_to_scores(t.logits)
-        if len(t) > 0:
+        if self.use_motion:
+            if self.motions is None:
+                from .motion import MotionState
+                self.motions = MotionState(self.motion_max_length, self.motion_min_length, t.boxes.device)
+            if len(t) > 0:
+                t.ids, t.disappear_time, t.last_appear_boxes = self.motions.observe(
+                    t.scores, t.labels, t.boxes, t.ids, t.disappear_time, t.last_appear_boxes,
+                    self.track_score_thresh, self.miss_tolerance)
+        elif len(t) > 0:
             own = t.scores.gather(1, t.labels[:, None]).squeeze(1)
             t.disappear_time = torch.where(own < self.track_score_thresh, t.disappear_time + 1,
                                            torch.zeros_like(t.disappear_time))
@@ -68,5 +81,8 @@ class RuntimeTracker:
         new.disappear_time = torch.zeros((n_new,), dtype=torch.long, device=device)
         new.labels = torch.max(new.scores, dim=-1).indices
         new.ids = torch.arange(self.max_obj_id, self.max_obj_id + n_new, dtype=torch.long, device=device)
+        if self.use_motion:
+            new.last_appear_boxes = new.boxes
+            self.motions.register(self.max_obj_id, new.boxes)
         self.max_obj_id += n_new
         return tracks, [new.to(device)]
