@@ -2,8 +2,8 @@
 step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so (training-clip augmentation),
 libstatic_clip_ops_hip.so (clips made from one still image), libtrack_eval_hip.so (HOTA / CLEAR / Identity
 evaluation), libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) and
-libtrack_motion_hip.so (the online tracker's motion post-process) with hipcc for gfx950 (cross-compiles without a
-GPU)."""
+libtrack_motion_hip.so (the online tracker's motion post-process) and libjpeg_ops_hip.so (JPEG decode: host entropy
+stage and device pixels) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -42,6 +42,10 @@ TRACK_EVAL_BDD_LIB = os.path.join(LIB_DIR, "libtrack_eval_bdd_hip.so")
 TRACK_MOTION_SRC = os.path.join(_HERE, "csrc", "track_motion.hip")
 TRACK_MOTION_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_motion_hip.h")
 TRACK_MOTION_LIB = os.path.join(LIB_DIR, "libtrack_motion_hip.so")
+JPEG_SRC = os.path.join(_HERE, "csrc", "jpeg_ops.hip")
+JPEG_HDR = os.path.join(os.path.dirname(_HERE), "include", "jpeg_ops_hip.h")
+JPEG_CORE = os.path.join(_HERE, "csrc", "jpeg_entropy_core.h")
+JPEG_LIB = os.path.join(LIB_DIR, "libjpeg_ops_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -139,6 +143,13 @@ def build_track_motion_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(TRACK_MOTION_SRC, TRACK_MOTION_LIB, verbose, extra=("-ffp-contract=off",))
 
 
+def build_jpeg_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(JPEG_LIB, (JPEG_SRC, JPEG_HDR, JPEG_CORE)):
+        return JPEG_LIB
+    # int32 products of hostile coefficients wrap, as the numpy statement's do; the batch entry point starts threads
+    return _compile(JPEG_SRC, JPEG_LIB, verbose, extra=("-fwrapv", "-pthread"))
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
@@ -148,3 +159,4 @@ if __name__ == "__main__":
     print(build_track_eval_lib(force=True, verbose=True))
     print(build_track_eval_bdd_lib(force=True, verbose=True))
     print(build_track_motion_lib(force=True, verbose=True))
+    print(build_jpeg_lib(force=True, verbose=True))

@@ -19,6 +19,12 @@ From decoded frames (uint8, H x W x 3, e.g. what ``cv2.imread`` returns) instead
 ``track`` is ``step_raw(frame, next_frame)`` in a loop: upload through pinned memory, one kernel (data/frames.py),
 then the same encode / decode path as ``step``.
 
+From JPEG files or byte streams, the decode in front (data/jpeg.py: Huffman stage on one host thread, a frame ahead;
+IDCT and colour on the GPU, queued on the side stream with the rest of the next frame's work):
+
+    for frame_idx, result in tracker.track_jpeg(paths, bgr=False):
+        lines += tracker.mot_lines(frame_idx, result)
+
 ``use_motion=True`` (the reference's ``USE_MOTION``): after the query updater, the reference point of every track that
 is being missed is moved along its mean box velocity (models/motion.py: device state, one launch, no synchronisation).
 """
@@ -198,6 +204,57 @@ class SequenceTracker:
             nxt = next(it, done)
             yield idx, self.step_raw(cur, None if nxt is done else nxt, bgr=bgr)
             cur, idx = nxt, idx + 1
+
+    def track_jpeg(self, files_or_bytes, *, bgr: bool = False):
+        """``track`` with the decode in front: an iterable of JPEG paths or byte streams, yields ``(frame_idx,
+        result)``.  ``bgr``: the channel order the frames are decoded to (the model sees the same either way).
+
+        While frame i runs, one worker thread Huffman-decodes frame i + 2 into a pinned buffer (ctypes releases the
+        interpreter lock for the call), and frame i + 1's coefficients are uploaded and turned into pixels on the side
+        stream, in front of its resize and encode half that ``step_raw`` queues there.  The results are those of
+        ``track`` on the same frames decoded by Pillow: the pixels are equal byte for byte."""
+        if self.device.type != "cuda":
+            from .data.jpeg import decode_jpeg
+            yield from self.track((decode_jpeg(x, "cpu", bgr=bgr) for x in files_or_bytes), bgr=bgr)
+            return
+        from concurrent.futures import ThreadPoolExecutor
+        from .data import jpeg as J
+        staging = J._Staging(3)             # written by the worker / being copied / copied a frame ago
+
+        def entropy(item):
+            a = J._as_bytes(item)
+            try:
+                buf, slot = staging.take(J._frame_words(J.parse_jpeg(a)))
+                return J.entropy_decode(a, pinned=buf), slot
+            except J.UnsupportedJpeg as e:  # a stream only Pillow reads: decoded on the host, uploaded as pixels
+                return J._fallback(a, torch.device("cpu"), bgr, e), None
+
+        def pixels(job, stream):
+            coefs, slot = job
+            with torch.cuda.stream(stream):
+                if slot is None:
+                    return self._upload(coefs)
+                frame = J._device_stage(coefs.flat[None], coefs.info, 1, self.device, bgr)[0]
+                staging.copied(slot, stream.record_event())
+            return frame
+
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        it = iter(files_or_bytes)
+        done = object()
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            ahead = lambda: (lambda x: None if x is done else pool.submit(entropy, x))(next(it, done))  # noqa: E731
+            first, job = ahead(), ahead()
+            if first is None:
+                return
+            cur, idx = pixels(first.result(), torch.cuda.current_stream(self.device)), 0
+            while cur is not None:
+                nxt = None
+                if job is not None:
+                    decoded, job = job.result(), ahead()
+                    nxt = pixels(decoded, self._side)
+                yield idx, self.step_raw(cur, nxt, bgr=bgr)
+                cur, idx = nxt, idx + 1
 
     def _upload(self, frame_u8) -> torch.Tensor:
         """The frame on the device, copied on the current stream.  Pageable host memory goes through one of two pinned
