@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define CLIPOPS_ABI_VERSION 10
+#define CLIPOPS_ABI_VERSION 11
 
 int clipops_abi_version(void);
 const char *clipops_last_error(void);
@@ -157,6 +157,23 @@ int clipops_add_layer_norm_fwd_f32(const float *x, const float *res, const float
  * layer_norm_grad_input + two gamma/beta kernels + the add's fan-out. */
 int clipops_add_layer_norm_bwd_f32(const float *grad_y, const float *sum, const float *stats, const float *gamma,
                                    long rows, int chunk_rows, float *grad_sum, float *partial, void *stream);
+
+/* ---- the encoder layer's fan-ins folded into the LayerNorm kernels (ABI 11) ----
+ * Forward with a second output q = y + pos (all (rows,256)), written in the same pass from the y in registers: the next
+ * encoder layer's query (reference models/deformable_encoder.py:88-90, with_pos_embed), otherwise an element-wise add
+ * over the tensor this kernel has just written.  sum / y / stats are bit for bit those of clipops_add_layer_norm_fwd_f32,
+ * q is the fp32 sum y + pos. */
+int clipops_add_layer_norm_pos_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta,
+                                       const float *pos, long rows, float eps, float *sum, float *y, float *q,
+                                       float *stats, void *stream);
+/* Backward for an output with up to three consumers: grad_y = (g0 + g1) + g2 over the NON-NULL slots in slot order (at
+ * least one), summed in registers -- the sum is never written.  grad_sum and partial as above.  colsum_partial
+ * (2 * ceil(rows/chunk_rows), 256) receives the per-chunk column sums of grad_sum (the bias gradient of the Linear that
+ * produced `res`), accumulated in fp64 and stored as two float rows per chunk (the fp32 value and its remainder);
+ * clipops_colsum_f32 over it yields the column sums rounded once.  No atomics: the results do not vary between runs. */
+int clipops_add_layer_norm_fanin_bwd_f32(const float *g0, const float *g1, const float *g2, const float *sum,
+                                         const float *stats, const float *gamma, long rows, int chunk_rows,
+                                         float *grad_sum, float *partial, float *colsum_partial, void *stream);
 
 /* Linear sum assignment of `n_problems` cost matrices of one shape (n_rows, n_cols) on the device -- what the
  * reference's matcher does on the host with scipy.optimize.linear_sum_assignment after a `.cpu()` copy

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libclip_ops_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_int, c_long, c_float, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 
@@ -42,6 +42,8 @@ SYMBOLS = {
                             [c_void_p, c_long, c_long] * 3 + [c_void_p], c_int),
     "clipops_add_layer_norm_fwd_f32": ([c_void_p] * 4 + [c_long, c_float] + [c_void_p] * 4, c_int),
     "clipops_add_layer_norm_bwd_f32": ([c_void_p] * 4 + [c_long, c_int] + [c_void_p] * 3, c_int),
+    "clipops_add_layer_norm_pos_fwd_f32": ([c_void_p] * 5 + [c_long, c_float] + [c_void_p] * 5, c_int),
+    "clipops_add_layer_norm_fanin_bwd_f32": ([c_void_p] * 6 + [c_long, c_int] + [c_void_p] * 4, c_int),
     "clipops_sine_embed_fwd_f32": ([c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_void_p, c_void_p], c_int),
     "clipops_sine_embed_bwd_f32": ([c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
                                    c_int),

@@ -752,12 +752,16 @@ __device__ __forceinline__ float wave_sum64(float x) {
     return x;
 }
 
+// WITH_Q (ABI 11): q = y + pos is written in the same pass from the y still in registers -- the next encoder layer's
+// query, which was a torch add (read 2, write 1 tensor) right after this kernel.  y is the same expression either way.
+template <bool WITH_Q>
 __global__ __launch_bounds__(256) void add_layer_norm_fwd_kernel(const float *__restrict__ x,
                                                                 const float *__restrict__ res,
                                                                 const float *__restrict__ gamma,
-                                                                const float *__restrict__ beta, long rows, float eps,
+                                                                const float *__restrict__ beta,
+                                                                const float *__restrict__ pos, long rows, float eps,
                                                                 float *__restrict__ sum, float *__restrict__ y,
-                                                                float *__restrict__ stats) {
+                                                                float *__restrict__ q, float *__restrict__ stats) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -772,7 +776,9 @@ __global__ __launch_bounds__(256) void add_layer_norm_fwd_kernel(const float *__
     const float rstd = rsqrtf(var + eps);
     const f32x4_t g = *reinterpret_cast<const f32x4_t *>(gamma + lane * 4);
     const f32x4_t be = *reinterpret_cast<const f32x4_t *>(beta + lane * 4);
-    *reinterpret_cast<f32x4_t *>(y + off) = (d * rstd) * g + be;
+    const f32x4_t yv = (d * rstd) * g + be;
+    *reinterpret_cast<f32x4_t *>(y + off) = yv;
+    if (WITH_Q) *reinterpret_cast<f32x4_t *>(q + off) = yv + *reinterpret_cast<const f32x4_t *>(pos + off);
     if (lane == 0) {
         stats[2 * row] = mean;
         stats[2 * row + 1] = rstd;
@@ -811,6 +817,63 @@ __global__ __launch_bounds__(256) void add_layer_norm_bwd_kernel(const float *__
     if (wave < 2) {                       // wave 0: gamma part, wave 1: beta part
         const f32x4_t t = (s_acc[0][wave][lane] + s_acc[1][wave][lane]) + (s_acc[2][wave][lane] + s_acc[3][wave][lane]);
         *reinterpret_cast<f32x4_t *>(partial + (long)blockIdx.x * 2 * CLIPOPS_LN_COLS + wave * CLIPOPS_LN_COLS + lane * 4) = t;
+    }
+}
+
+// The same backward for a LayerNorm whose output has up to three consumers (ABI 11): the incoming gradient is
+// (ga + gb) + gc, summed in registers (gb / gc may be null: skipped) and never written out, and the column sums of
+// grad_sum -- the bias gradient of the Linear that produced `res` -- ride along.  Those are kept in fp64 like every
+// column sum here and leave the workgroup as a float pair (hi, lo = the rounding remainder) in rows 2 * chunk and
+// 2 * chunk + 1 of `zpartial`: the finishing colsum adds both in fp64, so a chunk's sum is not rounded to fp32 on the way.
+__global__ __launch_bounds__(256) void add_layer_norm_bwd_fanin_kernel(const float *__restrict__ ga,
+                                                                      const float *__restrict__ gb,
+                                                                      const float *__restrict__ gc,
+                                                                      const float *__restrict__ sum,
+                                                                      const float *__restrict__ stats,
+                                                                      const float *__restrict__ gamma, long rows,
+                                                                      int chunk_rows, float *__restrict__ gsum,
+                                                                      float *__restrict__ partial,
+                                                                      float *__restrict__ zpartial) {
+    __shared__ f32x4_t s_acc[4][2][64];
+    __shared__ f64x4_t s_z[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f32x4_t gm = *reinterpret_cast<const f32x4_t *>(gamma + lane * 4);
+    f32x4_t acc_g = {0.f, 0.f, 0.f, 0.f}, acc_b = {0.f, 0.f, 0.f, 0.f};
+    f64x4_t acc_z = {0., 0., 0., 0.};
+    const long r0 = (long)blockIdx.x * chunk_rows;
+    const long r1 = r0 + chunk_rows < rows ? r0 + chunk_rows : rows;
+    for (long row = r0 + wave; row < r1; row += 4) {
+        const long off = row * CLIPOPS_LN_COLS + lane * 4;
+        f32x4_t g = *reinterpret_cast<const f32x4_t *>(ga + off);
+        if (gb) g += *reinterpret_cast<const f32x4_t *>(gb + off);
+        if (gc) g += *reinterpret_cast<const f32x4_t *>(gc + off);
+        const f32x4_t s = *reinterpret_cast<const f32x4_t *>(sum + off);
+        const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+        const f32x4_t xh = (s - mean) * rstd;
+        const f32x4_t gh = g * gm;
+        const float c1 = wave_sum64((gh.x + gh.y) + (gh.z + gh.w)) * (1.f / CLIPOPS_LN_COLS);
+        const float c2 = wave_sum64((gh.x * xh.x + gh.y * xh.y) + (gh.z * xh.z + gh.w * xh.w)) * (1.f / CLIPOPS_LN_COLS);
+        const f32x4_t dz = (gh - c1 - xh * c2) * rstd;
+        *reinterpret_cast<f32x4_t *>(gsum + off) = dz;
+        acc_g += g * xh;
+        acc_b += g;
+        acc_z.x += dz.x; acc_z.y += dz.y; acc_z.z += dz.z; acc_z.w += dz.w;
+    }
+    s_acc[wave][0][lane] = acc_g;
+    s_acc[wave][1][lane] = acc_b;
+    s_z[wave][lane] = acc_z;
+    __syncthreads();
+    if (wave < 2) {                       // wave 0: gamma part, wave 1: beta part
+        const f32x4_t t = (s_acc[0][wave][lane] + s_acc[1][wave][lane]) + (s_acc[2][wave][lane] + s_acc[3][wave][lane]);
+        *reinterpret_cast<f32x4_t *>(partial + (long)blockIdx.x * 2 * CLIPOPS_LN_COLS + wave * CLIPOPS_LN_COLS + lane * 4) = t;
+    } else if (wave == 2) {               // wave 2: the column sums of grad_sum
+        const f64x4_t t = (s_z[0][lane] + s_z[1][lane]) + (s_z[2][lane] + s_z[3][lane]);
+        const f32x4_t hi = {(float)t.x, (float)t.y, (float)t.z, (float)t.w};
+        const f32x4_t lo = {(float)(t.x - (double)hi.x), (float)(t.y - (double)hi.y), (float)(t.z - (double)hi.z),
+                            (float)(t.w - (double)hi.w)};
+        float *zp = zpartial + (long)blockIdx.x * 2 * CLIPOPS_LN_COLS + lane * 4;
+        *reinterpret_cast<f32x4_t *>(zp) = hi;
+        *reinterpret_cast<f32x4_t *>(zp + CLIPOPS_LN_COLS) = lo;
     }
 }
 
@@ -1373,9 +1436,21 @@ int clipops_add_layer_norm_fwd_f32(const float *x, const float *res, const float
     if (rows < 0) return fail(1, "clipops_add_layer_norm_fwd_f32: negative row count");
     if (rows == 0) { g_err[0] = 0; return 0; }
     if (!x || !res || !gamma || !beta || !sum || !y || !stats) return fail(1, "clipops_add_layer_norm_fwd_f32: null pointer");
-    hipLaunchKernelGGL(add_layer_norm_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x,
-                       res, gamma, beta, rows, eps, sum, y, stats);
+    hipLaunchKernelGGL(add_layer_norm_fwd_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       x, res, gamma, beta, nullptr, rows, eps, sum, y, nullptr, stats);
     return check_launch("add_layer_norm_fwd_kernel");
+}
+
+int clipops_add_layer_norm_pos_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta,
+                                       const float *pos, long rows, float eps, float *sum, float *y, float *q,
+                                       float *stats, void *stream) {
+    if (rows < 0) return fail(1, "clipops_add_layer_norm_pos_fwd_f32: negative row count");
+    if (rows == 0) { g_err[0] = 0; return 0; }
+    if (!x || !res || !gamma || !beta || !pos || !sum || !y || !q || !stats)
+        return fail(1, "clipops_add_layer_norm_pos_fwd_f32: null pointer");
+    hipLaunchKernelGGL(add_layer_norm_fwd_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       x, res, gamma, beta, pos, rows, eps, sum, y, q, stats);
+    return check_launch("add_layer_norm_fwd_kernel<pos>");
 }
 
 int clipops_add_layer_norm_bwd_f32(const float *grad_y, const float *sum, const float *stats, const float *gamma,
@@ -1387,6 +1462,25 @@ int clipops_add_layer_norm_bwd_f32(const float *grad_y, const float *sum, const 
     hipLaunchKernelGGL(add_layer_norm_bwd_kernel, dim3((unsigned)((rows + chunk_rows - 1) / chunk_rows)), dim3(256), 0,
                        (hipStream_t)stream, grad_y, sum, stats, gamma, rows, chunk_rows, grad_sum, partial);
     return check_launch("add_layer_norm_bwd_kernel");
+}
+
+int clipops_add_layer_norm_fanin_bwd_f32(const float *g0, const float *g1, const float *g2, const float *sum,
+                                         const float *stats, const float *gamma, long rows, int chunk_rows,
+                                         float *grad_sum, float *partial, float *colsum_partial, void *stream) {
+    if (rows < 0 || chunk_rows <= 0) return fail(1, "clipops_add_layer_norm_fanin_bwd_f32: bad dimension");
+    if (rows == 0) { g_err[0] = 0; return 0; }
+    const float *g[3] = {nullptr, nullptr, nullptr};      // the non-null slots, in slot order
+    int n = 0;
+    if (g0) g[n++] = g0;
+    if (g1) g[n++] = g1;
+    if (g2) g[n++] = g2;
+    if (n == 0) return fail(1, "clipops_add_layer_norm_fanin_bwd_f32: no gradient input");
+    if (!sum || !stats || !gamma || !grad_sum || !partial || !colsum_partial)
+        return fail(1, "clipops_add_layer_norm_fanin_bwd_f32: null pointer");
+    hipLaunchKernelGGL(add_layer_norm_bwd_fanin_kernel, dim3((unsigned)((rows + chunk_rows - 1) / chunk_rows)), dim3(256), 0,
+                       (hipStream_t)stream, g[0], g[1], g[2], sum, stats, gamma, rows, chunk_rows, grad_sum, partial,
+                       colsum_partial);
+    return check_launch("add_layer_norm_bwd_fanin_kernel");
 }
 
 int clipops_assign_f32(const float *cost, long stride_problem, long stride_row, long stride_col, int n_problems,

@@ -669,14 +669,7 @@ LN_COLS = 256
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, eps):
-        rows = x.numel() // LN_COLS
-        s = torch.empty_like(x)
-        y = torch.empty_like(x)
-        stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-        L = _lib()
-        L.check(L.lib.clipops_add_layer_norm_fwd_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                                     rows, eps, s.data_ptr(), y.data_ptr(), stats.data_ptr(), _stream(x)),
-                "clipops_add_layer_norm_fwd_f32")
+        s, y, _, stats = add_layer_norm_fwd(x, res, weight, bias, eps)
         ctx.save_for_backward(s, stats, weight)
         return y
 
@@ -694,6 +687,63 @@ class _AddLayerNorm(torch.autograd.Function):
                 "clipops_add_layer_norm_bwd_f32")
         gwb = colsum(partial)                       # [grad_gamma | grad_beta]
         return gs, gs, gwb[:LN_COLS], gwb[LN_COLS:], None
+
+
+def add_layer_norm_fwd(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                       pos: torch.Tensor = None):
+    """The forward kernel on contiguous fp32 (..., 256) tensors, outside autograd: (sum, y, q, stats) with
+    q = y + pos from the same pass when ``pos`` is given (None otherwise); sum / stats are what the backward takes."""
+    rows = x.numel() // LN_COLS
+    s, y = torch.empty_like(x), torch.empty_like(x)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    L = _lib()
+    if pos is None:
+        L.check(L.lib.clipops_add_layer_norm_fwd_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                                     rows, eps, s.data_ptr(), y.data_ptr(), stats.data_ptr(), _stream(x)),
+                "clipops_add_layer_norm_fwd_f32")
+        return s, y, None, stats
+    assert pos.shape == x.shape and pos.is_contiguous() and pos.dtype == torch.float32
+    q = torch.empty_like(x)
+    L.check(L.lib.clipops_add_layer_norm_pos_fwd_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                                     pos.data_ptr(), rows, eps, s.data_ptr(), y.data_ptr(), q.data_ptr(),
+                                                     stats.data_ptr(), _stream(x)), "clipops_add_layer_norm_pos_fwd_f32")
+    return s, y, q, stats
+
+
+def _fanin_chunk_rows(rows: int) -> int:
+    """Rows per workgroup of the fan-in backward: as the plain backward for short inputs; for long ones at most 1024
+    chunks, so that the 2 rows per chunk of the column-sum partials stay within one pass of the finishing kernel."""
+    if rows <= 4096:
+        return 16
+    per_chunk = -(-rows // 1024)
+    return max(64, (per_chunk + 3) // 4 * 4)
+
+
+def add_layer_norm_bwd_fanin(grads, s: torch.Tensor, stats: torch.Tensor, weight: torch.Tensor):
+    """Backward of add_layer_norm for an output with up to three consumers: ``grads`` = (g0, g1, g2), contiguous fp32
+    tensors shaped like ``s`` or None; the kernel sums the given ones in slot order in registers.  Returns
+    (grad_sum, grad_gamma, grad_beta, column sums of grad_sum) -- the last is the bias gradient of the Linear whose
+    output was the residual branch, from the same pass (fp64 sums, rounded once; no atomics)."""
+    g0, g1, g2 = grads
+    for g in grads:
+        assert g is None or (g.is_contiguous() and g.dtype == torch.float32 and g.numel() == s.numel())
+    rows = s.numel() // LN_COLS
+    chunk = _fanin_chunk_rows(rows)
+    chunks = -(-rows // chunk)
+    gs = torch.empty_like(s)
+    partial = torch.empty((chunks, 2 * LN_COLS), dtype=torch.float32, device=s.device)
+    zpartial = torch.empty((2 * chunks, LN_COLS), dtype=torch.float32, device=s.device)
+    out = torch.empty((3 * LN_COLS,), dtype=torch.float32, device=s.device)
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    L = _lib()
+    st = _stream(s)
+    L.check(L.lib.clipops_add_layer_norm_fanin_bwd_f32(ptr(g0), ptr(g1), ptr(g2), s.data_ptr(), stats.data_ptr(),
+                                                       weight.data_ptr(), rows, chunk, gs.data_ptr(), partial.data_ptr(),
+                                                       zpartial.data_ptr(), st), "clipops_add_layer_norm_fanin_bwd_f32")
+    L.check(L.lib.clipops_colsum_f32(partial.data_ptr(), chunks, 2 * LN_COLS, out.data_ptr(), st), "clipops_colsum_f32")
+    L.check(L.lib.clipops_colsum_f32(zpartial.data_ptr(), 2 * chunks, LN_COLS, out.data_ptr() + 8 * LN_COLS, st),
+            "clipops_colsum_f32")
+    return gs, out[:LN_COLS], out[LN_COLS:2 * LN_COLS], out[2 * LN_COLS:]
 
 
 def add_layer_norm_supported(x: torch.Tensor, res: torch.Tensor, norm) -> bool:

@@ -6,18 +6,25 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
+from .. import MultiScaleDeformableAttention as MSDA
 from ..modules import MSDeformAttn
+from ..modules import linear as linear_mod
+from ..modules import ms_deform_attn as msda_mod
+from ..functions import clip_ops, encoder_layer
 from ..functions.clip_ops import add_layer_norm
 from ..modules.linear import long_linear
 from .utils import get_activation_layer, get_clones
 
 
 class DeformableEncoder(nn.Module):
-    def __init__(self, encoder_layer, num_layers, use_checkpoint: bool):
+    def __init__(self, encoder_layer, num_layers, use_checkpoint: bool, layer_node: bool = True):
         super().__init__()
         self.layers = get_clones(module=encoder_layer, n=num_layers)
         self.num_layers = num_layers
         self.use_checkpoint = use_checkpoint
+        # layers as single autograd nodes (functions/encoder_layer.py); the owner switches it off when it wraps the
+        # encoder in activation checkpointing
+        self.layer_node = layer_node
 
     @staticmethod
     def get_reference_points(spatial_shapes, valid_ratios, device):
@@ -51,8 +58,14 @@ class DeformableEncoder(nn.Module):
             for first in range(0, self.num_layers, 3):
                 output = checkpoint(run_group, output, first, use_reentrant=False)
             return output
-        for layer in self.layers:
-            output = layer(output, pos, reference_points, spatial_shapes, level_start_index, padding_mask)
+        if not self.layer_node:
+            for layer in self.layers:
+                output = layer(output, pos, reference_points, spatial_shapes, level_start_index, padding_mask)
+            return output
+        q = None        # a layer that ran as one node hands the next one its query, output + pos, from its last kernel
+        for i, layer in enumerate(self.layers):
+            output, q = layer(output, pos, reference_points, spatial_shapes, level_start_index, padding_mask, q=q,
+                              emit_q=i + 1 < self.num_layers)
         return output
 
 
@@ -79,8 +92,53 @@ class DeformableEncoderLayer(nn.Module):
         hidden = self.dropout2(long_linear(src, self.linear1.weight, self.linear1.bias, activation=self.activation))
         return add_layer_norm(src, self.dropout3(long_linear(hidden, self.linear2.weight, self.linear2.bias)), self.norm2)
 
-    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
-        attn = self.self_attn(self.with_pos_embed(src, pos), reference_points, src, spatial_shapes,
+    def node_usable(self, src, pos, reference_points) -> bool:
+        """Whether this call can run as ``EncoderLayerNode``: fp32 CUDA training-graph calls of the configuration the
+        fused operator and the 256-wide LayerNorm kernels cover, with nothing between the sublayers (no active dropout)."""
+        at = self.self_attn
+        return (encoder_layer.enabled() and pos is not None and src.is_cuda and src.dim() == 3 and pos.shape == src.shape
+                and src.dtype == torch.float32 and pos.dtype == torch.float32
+                and torch.is_grad_enabled() and not torch.is_autocast_enabled()
+                and not torch.cuda.is_current_stream_capturing()
+                and not (self.training and any(d.p > 0 for d in (self.dropout1, self.dropout2, self.dropout3)))
+                and isinstance(self.activation, nn.ReLU) and linear_mod.FUSE_RELU_EPILOGUE
+                and msda_mod.FUSED_PROLOGUE and not at.sigmoid_attn
+                and MSDA.fused_supported(src.dtype, at.d_model // at.n_heads, at.n_levels, at.n_points)
+                and reference_points.dtype == torch.float32 and not reference_points.requires_grad
+                and reference_points.shape[-1] in (2, 4)
+                and clip_ops.add_layer_norm_supported(src, src, self.norm1)
+                and clip_ops.add_layer_norm_supported(src, src, self.norm2)
+                and all(p.requires_grad and p.dtype == torch.float32 for p in self.parameters()))
+
+    def forward_node(self, src, q, pos_next, reference_points, spatial_shapes, level_start_index, padding_mask):
+        """The layer as one autograd node: (output, output + pos_next or None)."""
+        at = self.self_attn
+        site = at.__dict__.get("_msda_site")
+        if site is None:
+            site = at.__dict__["_msda_site"] = MSDA.new_call_site()
+        # (as MSDeformAttn.forward: a mask that carries its padded rows is applied by zeroing those rows of `value`)
+        mask = padding_mask
+        rows = getattr(mask, msda_mod.MASKED_ROWS_ATTR, None) if mask is not None else None
+        if rows is not None:
+            mask = None
+        wq, bq = at._fused_query_projection()
+        return encoder_layer.EncoderLayerNode.apply(
+            src.contiguous(), q.contiguous(), None if pos_next is None else pos_next.contiguous(),
+            reference_points.contiguous(), spatial_shapes, level_start_index,
+            None if mask is None else mask.contiguous(), rows, at.n_heads, at.n_points, site, float(self.norm1.eps),
+            float(self.norm2.eps), at.value_proj.weight, at.value_proj.bias, wq, bq, at.output_proj.weight,
+            at.output_proj.bias, self.norm1.weight, self.norm1.bias, self.linear1.weight, self.linear1.bias,
+            self.linear2.weight, self.linear2.bias, self.norm2.weight, self.norm2.bias)
+
+    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None, q=None,
+                emit_q=None):
+        """``emit_q`` given (the encoder's loop): returns (output, query of the next layer or None) and may run as one
+        autograd node; ``q``: this layer's query ``src + pos`` when the layer in front produced it."""
+        if emit_q is not None and self.node_usable(src, pos, reference_points):
+            return self.forward_node(src, self.with_pos_embed(src, pos) if q is None else q, pos if emit_q else None,
+                                     reference_points, spatial_shapes, level_start_index, padding_mask)
+        attn = self.self_attn(self.with_pos_embed(src, pos) if q is None else q, reference_points, src, spatial_shapes,
                               level_start_index, padding_mask)
         src = add_layer_norm(src, self.dropout1(attn), self.norm1)
-        return self.forward_ffn(src)
+        out = self.forward_ffn(src)
+        return out if emit_q is None else (out, None)

@@ -45,7 +45,8 @@ class DeformableTransformer(nn.Module):
                                                sigmoid_attn=False, extra_track_attn=extra_track_attn,
                                                n_det_queries=n_det_queries, visualize=visualize)
         self.encoder = DeformableEncoder(encoder_layer, n_enc_layers,
-                                         use_checkpoint=(use_checkpoint and checkpoint_level == 1))
+                                         use_checkpoint=(use_checkpoint and checkpoint_level == 1),
+                                         layer_node=not use_checkpoint)
         self.decoder = DeformableDecoder(decoder_layer, n_dec_layers, return_intermediate=return_intermediate_dec,
                                          merge_det_track_layer=merge_det_track_layer, n_det_queries=n_det_queries,
                                          d_model=d_model, use_checkpoint=use_checkpoint, use_dab=use_dab,

@@ -76,6 +76,25 @@ AMP_SPLITK = os.environ.get("MEMOTR_AMP_SPLITK", "1") != "0"      # autocast: lo
 AMP_MIN_ROWS = 256       # ... from this many rows on (below, torch's bias-gradient reduction is a single block)
 
 
+def dgrad_blas(rows: int) -> str:
+    """The library of a long linear's input-gradient GEMM (see configure_blas)."""
+    return "cublas" if rows >= ROCBLAS_DGRAD_ROWS else "cublaslt"
+
+
+def splitk_weight_grad(g2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+    """dW = g2^T x2 for (rows, N) and (rows, K) matrices with the contraction over the rows split into chunks: one
+    batched GEMM and a sum of the partial products (module docstring)."""
+    rows, N, K = x2.shape[0], g2.shape[1], x2.shape[1]
+    c = _pick_chunks(rows)
+    r = rows // c
+    main = r * c
+    with (prefer_blas("cublaslt") if g2.is_cuda else contextlib.nullcontext()):
+        gw = torch.bmm(g2[:main].view(c, r, N).transpose(1, 2), x2[:main].view(c, r, K)).sum(0)
+        if main < rows:
+            gw = gw + g2[main:].t() @ x2[main:]
+    return gw
+
+
 class _SplitKLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, relu=False):
@@ -113,20 +132,10 @@ class _SplitKLinear(torch.autograd.Function):
         cdt = g2.dtype                      # bf16 under autocast (forward ran in bf16), else the parameter dtype
         on_gpu = g2.is_cuda
         if ctx.needs_input_grad[0]:
-            lib = "cublas" if g2.shape[0] >= ROCBLAS_DGRAD_ROWS else "cublaslt"
-            with (prefer_blas(lib) if on_gpu else contextlib.nullcontext()):
+            with (prefer_blas(dgrad_blas(g2.shape[0])) if on_gpu else contextlib.nullcontext()):
                 gx = (g2 @ weight.to(cdt)).view(x.shape).to(x.dtype)
         if ctx.needs_input_grad[1]:
-            x2 = x.reshape(-1, K).to(cdt)
-            rows = x2.shape[0]
-            c = _pick_chunks(rows)
-            r = rows // c
-            main = r * c
-            with (prefer_blas("cublaslt") if on_gpu else contextlib.nullcontext()):
-                gw = torch.bmm(g2[:main].view(c, r, N).transpose(1, 2), x2[:main].view(c, r, K)).sum(0)
-                if main < rows:
-                    gw = gw + g2[main:].t() @ x2[main:]
-            gw = gw.to(weight.dtype)
+            gw = splitk_weight_grad(g2, x.reshape(-1, K).to(cdt)).to(weight.dtype)
         if gb_done is not None:
             gb = gb_done.to(weight.dtype)
         elif ctx.has_bias and ctx.needs_input_grad[2]:
