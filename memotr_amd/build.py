@@ -3,7 +3,8 @@ step), libframe_ops_hip.so (raw-frame resize / normalise), libaugment_ops_hip.so
 libstatic_clip_ops_hip.so (clips made from one still image), libtrack_eval_hip.so (HOTA / CLEAR / Identity
 evaluation), libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) and
 libtrack_motion_hip.so (the online tracker's motion post-process) and libjpeg_ops_hip.so (JPEG decode: host entropy
-stage and device pixels) with hipcc for gfx950 (cross-compiles without a GPU)."""
+stage and device pixels), libjpeg_enc_hip.so (JPEG encode: device coefficients and host Huffman stage) and
+libtrack_draw_hip.so (track overlay) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -46,6 +47,13 @@ JPEG_SRC = os.path.join(_HERE, "csrc", "jpeg_ops.hip")
 JPEG_HDR = os.path.join(os.path.dirname(_HERE), "include", "jpeg_ops_hip.h")
 JPEG_CORE = os.path.join(_HERE, "csrc", "jpeg_entropy_core.h")
 JPEG_LIB = os.path.join(LIB_DIR, "libjpeg_ops_hip.so")
+JPEG_ENC_SRC = os.path.join(_HERE, "csrc", "jpeg_enc.hip")
+JPEG_ENC_HDR = os.path.join(os.path.dirname(_HERE), "include", "jpeg_enc_hip.h")
+JPEG_ENC_CORE = os.path.join(_HERE, "csrc", "jpeg_encode_core.h")
+JPEG_ENC_LIB = os.path.join(LIB_DIR, "libjpeg_enc_hip.so")
+TRACK_DRAW_SRC = os.path.join(_HERE, "csrc", "track_draw.hip")
+TRACK_DRAW_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_draw_hip.h")
+TRACK_DRAW_LIB = os.path.join(LIB_DIR, "libtrack_draw_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -150,6 +158,18 @@ def build_jpeg_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(JPEG_SRC, JPEG_LIB, verbose, extra=("-fwrapv", "-pthread"))
 
 
+def build_jpeg_enc_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(JPEG_ENC_LIB, (JPEG_ENC_SRC, JPEG_ENC_HDR, JPEG_ENC_CORE)):
+        return JPEG_ENC_LIB
+    return _compile(JPEG_ENC_SRC, JPEG_ENC_LIB, verbose, extra=("-pthread",))     # the batch entry point starts threads
+
+
+def build_track_draw_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(TRACK_DRAW_LIB, (TRACK_DRAW_SRC, TRACK_DRAW_HDR)):
+        return TRACK_DRAW_LIB
+    return _compile(TRACK_DRAW_SRC, TRACK_DRAW_LIB, verbose)
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
@@ -160,3 +180,5 @@ if __name__ == "__main__":
     print(build_track_eval_bdd_lib(force=True, verbose=True))
     print(build_track_motion_lib(force=True, verbose=True))
     print(build_jpeg_lib(force=True, verbose=True))
+    print(build_jpeg_enc_lib(force=True, verbose=True))
+    print(build_track_draw_lib(force=True, verbose=True))

@@ -25,6 +25,12 @@ IDCT and colour on the GPU, queued on the side stream with the rest of the next 
     for frame_idx, result in tracker.track_jpeg(paths, bgr=False):
         lines += tracker.mot_lines(frame_idx, result)
 
+With an annotated JPEG per frame on the side (render.py: boxes and ids drawn and the frame encoded on the GPU, the
+Huffman stage and the file a frame behind on one worker thread):
+
+    with AnnotatedWriter("out/") as writer:
+        for frame_idx, result in tracker.track_annotated(frames_or_paths, writer): ...
+
 ``use_motion=True`` (the reference's ``USE_MOTION``): after the query updater, the reference point of every track that
 is being missed is moved along its mean box velocity (models/motion.py: device state, one launch, no synchronisation).
 """
@@ -213,9 +219,14 @@ class SequenceTracker:
         interpreter lock for the call), and frame i + 1's coefficients are uploaded and turned into pixels on the side
         stream, in front of its resize and encode half that ``step_raw`` queues there.  The results are those of
         ``track`` on the same frames decoded by Pillow: the pixels are equal byte for byte."""
+        for idx, _, result in self._track_jpeg_frames(files_or_bytes, bgr):
+            yield idx, result
+
+    def _track_jpeg_frames(self, files_or_bytes, bgr: bool):
+        """The loop of ``track_jpeg``; yields ``(frame_idx, frame, result)`` with the decoded frame on the device."""
         if self.device.type != "cuda":
             from .data.jpeg import decode_jpeg
-            yield from self.track((decode_jpeg(x, "cpu", bgr=bgr) for x in files_or_bytes), bgr=bgr)
+            yield from self._track_frames((decode_jpeg(x, "cpu", bgr=bgr) for x in files_or_bytes), bgr)
             return
         from concurrent.futures import ThreadPoolExecutor
         from .data import jpeg as J
@@ -253,8 +264,55 @@ class SequenceTracker:
                 if job is not None:
                     decoded, job = job.result(), ahead()
                     nxt = pixels(decoded, self._side)
-                yield idx, self.step_raw(cur, nxt, bgr=bgr)
+                yield idx, cur, self.step_raw(cur, nxt, bgr=bgr)
                 cur, idx = nxt, idx + 1
+
+    def _track_frames(self, frames, bgr: bool):
+        """``track`` that keeps hold of the device copy: yields ``(frame_idx, frame on the device, result)``.  The
+        upload ``step_raw`` would make is made here, on the stream it would be made on (this frame's on the current
+        stream, the next frame's on the side stream), and ``step_raw`` is handed the device tensor: one upload."""
+        cuda = self.device.type == "cuda"
+        if cuda and self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+
+        def upload(frame, stream):
+            if not cuda:
+                return torch.from_numpy(frame) if not torch.is_tensor(frame) else frame
+            with torch.cuda.stream(stream):
+                return self._upload(frame)
+
+        it = iter(frames)
+        done = object()
+        first = next(it, done)
+        if first is done:
+            return
+        cur, idx = upload(first, torch.cuda.current_stream(self.device) if cuda else None), 0
+        while cur is not None:
+            nxt = next(it, done)
+            nxt = None if nxt is done else upload(nxt, self._side)
+            yield idx, cur, self.step_raw(cur, nxt, bgr=bgr)
+            cur, idx = nxt, idx + 1
+
+    def track_annotated(self, source, writer, *, bgr: bool = False):
+        """``track`` / ``track_jpeg`` with an annotated JPEG per frame on the side (render.AnnotatedWriter): ``source``
+        is an iterable of uint8 frames, or of JPEG paths / byte streams; yields exactly what they yield.  The writer is
+        handed the device copy of the frame the tracker already made -- no second upload -- and queues its draw and
+        encode launches on its own stream; ``bgr`` is the frames' channel order, for the model and the writer alike.
+        The caller closes the writer (it is a context manager)."""
+        import itertools
+        import os
+        it = iter(source)
+        done = object()
+        first = next(it, done)
+        if first is done:
+            return
+        stream_like = isinstance(first, (str, bytes, bytearray, memoryview, os.PathLike)) or \
+            (hasattr(first, "ndim") and first.ndim == 1)
+        items = itertools.chain([first], it)
+        frames = self._track_jpeg_frames(items, bgr) if stream_like else self._track_frames(items, bgr)
+        for idx, frame, result in frames:
+            writer.add(idx, frame, result, bgr=bgr)
+            yield idx, result
 
     def _upload(self, frame_u8) -> torch.Tensor:
         """The frame on the device, copied on the current stream.  Pageable host memory goes through one of two pinned
