@@ -4,7 +4,7 @@ libstatic_clip_ops_hip.so (clips made from one still image), libtrack_eval_hip.s
 evaluation), libtrack_eval_bdd_hip.so (BDD100K's class split and preprocessing in front of it) and
 libtrack_motion_hip.so (the online tracker's motion post-process) and libjpeg_ops_hip.so (JPEG decode: host entropy
 stage and device pixels), libjpeg_enc_hip.so (JPEG encode: device coefficients and host Huffman stage) and
-libtrack_draw_hip.so (track overlay) with hipcc for gfx950 (cross-compiles without a GPU)."""
+libtrack_draw_hip.so (track overlay) and libopt_ops_hip.so (gradient clipping + AdamW step) with hipcc for gfx950 (cross-compiles without a GPU)."""
 from __future__ import annotations
 
 import os
@@ -54,6 +54,9 @@ JPEG_ENC_LIB = os.path.join(LIB_DIR, "libjpeg_enc_hip.so")
 TRACK_DRAW_SRC = os.path.join(_HERE, "csrc", "track_draw.hip")
 TRACK_DRAW_HDR = os.path.join(os.path.dirname(_HERE), "include", "track_draw_hip.h")
 TRACK_DRAW_LIB = os.path.join(LIB_DIR, "libtrack_draw_hip.so")
+OPT_SRC = os.path.join(_HERE, "csrc", "opt_ops.hip")
+OPT_HDR = os.path.join(os.path.dirname(_HERE), "include", "opt_ops_hip.h")
+OPT_LIB = os.path.join(LIB_DIR, "libopt_ops_hip.so")
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -170,6 +173,13 @@ def build_track_draw_lib(force: bool = False, verbose: bool = False) -> str:
     return _compile(TRACK_DRAW_SRC, TRACK_DRAW_LIB, verbose)
 
 
+def build_opt_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not _stale(OPT_LIB, (OPT_SRC, OPT_HDR)):
+        return OPT_LIB
+    # every float32 operation of the update is rounded once, as include/opt_ops_hip.h states it: no fused multiply-add
+    return _compile(OPT_SRC, OPT_LIB, verbose, extra=("-ffp-contract=off",))
+
+
 if __name__ == "__main__":
     print(build_lib(force=True, verbose=True))
     print(build_clip_lib(force=True, verbose=True))
@@ -182,3 +192,4 @@ if __name__ == "__main__":
     print(build_jpeg_lib(force=True, verbose=True))
     print(build_jpeg_enc_lib(force=True, verbose=True))
     print(build_track_draw_lib(force=True, verbose=True))
+    print(build_opt_lib(force=True, verbose=True))

@@ -38,9 +38,19 @@ def get_param_groups(config: dict, model: nn.Module) -> Tuple[List[Dict], List[s
     return groups, ["lr_backbone", "lr_points", "lr_query_updater", "lr"]
 
 
-def build_optimizer(config: dict, model: nn.Module) -> torch.optim.Optimizer:
+def build_optimizer(config: dict, model: nn.Module, impl: str = None) -> torch.optim.Optimizer:
+    """The reference's AdamW over its four groups.  ``impl="hip"`` (or the environment variable MEMOTR_OPTIMIZER=hip
+    when ``impl`` is None): ``optim.ClipAdamW``, clipping and update as the project's own two launches; ``optimizer_step``
+    recognises it.  Otherwise torch's AdamW, as before."""
     groups, _ = get_param_groups(config, model)
     kwargs = dict(lr=config["LR"], weight_decay=config["WEIGHT_DECAY"])
+    if impl is None:
+        impl = os.environ.get("MEMOTR_OPTIMIZER") or None
+    if impl == "hip":
+        from .optim import ClipAdamW
+        return ClipAdamW(groups, **kwargs)
+    if impl not in (None, "torch"):
+        raise ValueError(f"Do not support optimizer implementation '{impl}' (\"hip\" or \"torch\")")
     on_gpu = any(p.is_cuda for g in groups for p in g["params"])
     if on_gpu:      # same update rule as the reference's AdamW, one multi-tensor kernel instead of a foreach chain
         try:
@@ -312,7 +322,13 @@ def clip_forward_backward(model: nn.Module, criterion, batch: dict, device, use_
 
 
 def optimizer_step(model: nn.Module, optimizer: torch.optim.Optimizer, max_norm: float):
-    """clip_grad_norm_ with the reference's hard-coded 0.1 whenever clipping is on (train_engine.py:241-246)."""
+    """clip_grad_norm_ with the reference's hard-coded 0.1 whenever clipping is on (train_engine.py:241-246).
+    A ``ClipAdamW`` clips inside its own step and the total gradient norm (a device scalar, not read here) is returned."""
+    from .optim import ClipAdamW
+    if isinstance(optimizer, ClipAdamW):
+        norm = optimizer.step(max_norm=0.1 if max_norm > 0 else None)
+        optimizer.zero_grad()
+        return norm
     if max_norm > 0:
         torch.nn.utils.clip_grad_norm_(model.parameters(), 0.1)
     optimizer.step()
