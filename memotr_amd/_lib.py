@@ -8,8 +8,9 @@ from __future__ import annotations
 import ctypes
 import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("MEMOTR_MSDA_LIB") or os.path.join(_HERE, "lib", "libmsda_hip.so")   # (override: A/B builds)
+from . import _cabi
+
+LIB_PATH = os.environ.get("MEMOTR_MSDA_LIB") or _cabi.lib_path("libmsda_hip.so")   # (override: A/B builds)
 
 ABI_VERSION = 7
 
@@ -64,27 +65,8 @@ SYMBOLS = {
 }
 
 
-def _load() -> ctypes.CDLL:
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -m memotr_amd.build` "
-            "(hipcc --offload-arch=gfx950). memotr_amd has no CPU fallback.")
-    # torch ships its own libamdhip64 (same SONAME); importing it first makes the HIP
-    # library bind to the runtime torch's streams/allocations live in.
-    import torch  # noqa: F401
-
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.argtypes = argtypes
-        fn.restype = restype
-    got = lib.msda_abi_version()
-    if got != ABI_VERSION:
-        raise ImportError(f"libmsda_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild the library")
-    return lib
-
-
-lib = _load()
+lib, check = _cabi.bind("libmsda_hip.so", "msda", SYMBOLS, ABI_VERSION, path=LIB_PATH,
+                        missing_note=" memotr_amd has no CPU fallback.")
 
 
 def last_error() -> str:

@@ -6,12 +6,12 @@ Like the other libraries there is no substitute: ``optim.ClipAdamW`` on CUDA par
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libopt_ops_hip.so")
+from . import _cabi
+
+LIB_PATH = _cabi.lib_path("libopt_ops_hip.so")
 
 ABI_VERSION = 1
 CHUNK = 16384                   # OPTSTEP_CHUNK
@@ -47,26 +47,4 @@ SYMBOLS = {
 }
 
 
-def _load() -> ctypes.CDLL:
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -m memotr_amd.build` "
-                          "(hipcc --offload-arch=gfx950).")
-    import torch  # noqa: F401  (binds the HIP runtime torch's streams live in; see _lib.py)
-
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    got = lib.optstep_abi_version()
-    if got != ABI_VERSION:
-        raise ImportError(f"libopt_ops_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild the library")
-    return lib
-
-
-lib = _load()
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib.optstep_last_error().decode()}")
+lib, check = _cabi.bind("libopt_ops_hip.so", "optstep", SYMBOLS, ABI_VERSION)

@@ -6,10 +6,10 @@ the library.  (Without a CUDA ``device`` it is the numpy / scipy statement of th
 from __future__ import annotations
 
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libtrack_eval_hip.so")
+from . import _cabi
+
+LIB_PATH = _cabi.lib_path("libtrack_eval_hip.so")
 
 ABI_VERSION = 1
 MAX_DIM = 2048          # TRACKEVAL_MAX_DIM
@@ -43,26 +43,4 @@ SYMBOLS = {
 }
 
 
-def _load() -> ctypes.CDLL:
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -m memotr_amd.build` "
-                          "(hipcc --offload-arch=gfx950).")
-    import torch  # noqa: F401  (binds the HIP runtime torch's streams live in; see _lib.py)
-
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    got = lib.trackeval_abi_version()
-    if got != ABI_VERSION:
-        raise ImportError(f"libtrack_eval_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild the library")
-    return lib
-
-
-lib = _load()
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib.trackeval_last_error().decode()}")
+lib, check = _cabi.bind("libtrack_eval_hip.so", "trackeval", SYMBOLS, ABI_VERSION)

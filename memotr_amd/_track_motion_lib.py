@@ -6,10 +6,10 @@ library.  (On CPU tensors it is the torch statement of the same definition that 
 from __future__ import annotations
 
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libtrack_motion_hip.so")
+from . import _cabi
+
+LIB_PATH = _cabi.lib_path("libtrack_motion_hip.so")
 
 ABI_VERSION = 1
 MAX_LENGTH = 16                 # TRACKMOTION_MAX_LENGTH
@@ -35,26 +35,4 @@ SYMBOLS = {
 }
 
 
-def _load() -> ctypes.CDLL:
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(f"{LIB_PATH} is missing: build it with `python -m memotr_amd.build` "
-                          "(hipcc --offload-arch=gfx950).")
-    import torch  # noqa: F401  (binds the HIP runtime torch's streams live in; see _lib.py)
-
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
-    got = lib.trackmotion_abi_version()
-    if got != ABI_VERSION:
-        raise ImportError(f"libtrack_motion_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild the library")
-    return lib
-
-
-lib = _load()
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib.trackmotion_last_error().decode()}")
+lib, check = _cabi.bind("libtrack_motion_hip.so", "trackmotion", SYMBOLS, ABI_VERSION)

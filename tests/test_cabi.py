@@ -5,21 +5,15 @@ must work without a device.
 """
 import ctypes
 import os
-import re
 
 import pytest
 
+from cabi_helpers import assert_binding_matches_header, declared_symbols
 from conftest import ROOT
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "msda_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(msda_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_header_declares_the_expected_entry_points():
-    syms = declared_symbols()
+    syms = declared_symbols("msda_hip.h", "msda")
     for s in ("msda_forward_f32", "msda_forward_f64", "msda_forward_bf16", "msda_backward_f32",
               "msda_backward_f64", "msda_backward_bf16", "msda_sample_indices_f32", "msda_abi_version",
               "msda_last_error", "msda_last_kernel", "msda_set_option", "msda_get_option"):
@@ -27,10 +21,7 @@ def test_header_declares_the_expected_entry_points():
 
 
 def test_library_exports_every_declared_symbol(hip_lib):
-    raw = ctypes.CDLL(hip_lib.LIB_PATH)
-    for s in declared_symbols():
-        assert hasattr(raw, s), f"libmsda_hip.so does not export {s}"
-    assert sorted(hip_lib.SYMBOLS) == declared_symbols()
+    assert_binding_matches_header(hip_lib, "msda_hip.h", "msda")
 
 
 def test_abi_version_and_options(hip_lib):

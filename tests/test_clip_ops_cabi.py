@@ -1,28 +1,14 @@
 """CPU: libclip_ops_hip.so loads and exports exactly what include/clip_ops_hip.h declares; argument validation is
 host-side and works without a device; CPU tensors take the element-wise formulation."""
 import ctypes
-import os
-import re
 
 import torch
 
-from conftest import ROOT
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "clip_ops_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(clipops_[a-z0-9_]+)\s*\(", text)))
+from cabi_helpers import assert_binding_matches_header
 
 
 def test_library_exports_every_declared_symbol(clip_lib):
-    raw = ctypes.CDLL(clip_lib.LIB_PATH)
-    syms = declared_symbols()
-    assert len(syms) >= 7
-    for s in syms:
-        assert hasattr(raw, s), f"libclip_ops_hip.so does not export {s}"
-    assert sorted(clip_lib.SYMBOLS) == syms
-    assert clip_lib.lib.clipops_abi_version() == clip_lib.ABI_VERSION
+    assert len(assert_binding_matches_header(clip_lib, "clip_ops_hip.h", "clipops")) >= 7
 
 
 def test_argument_errors_are_reported_without_a_device(clip_lib):

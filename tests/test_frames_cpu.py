@@ -2,14 +2,12 @@
 float64 bilinear interpolation, its exact properties (identity, constants, padding, channel order, strides, ``out=``),
 the C ABI of libframe_ops_hip.so without a device, and SequenceTracker.step_raw / track against step."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from cabi_helpers import assert_binding_matches_header
 from model_helpers import build_small_memotr, patch_operator
 
 from memotr_amd.data import frames as F
@@ -178,22 +176,9 @@ def frame_lib():
     return _frame_lib
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "frame_ops_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(frameops_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_declared_symbol(frame_lib):
-    raw = ctypes.CDLL(frame_lib.LIB_PATH)
-    syms = declared_symbols()
+    syms = assert_binding_matches_header(frame_lib, "frame_ops_hip.h", "frameops", "FRAMEOPS_ABI_VERSION")
     assert syms == ["frameops_abi_version", "frameops_last_error", "frameops_resize_normalize_u8"]
-    for s in syms:
-        assert hasattr(raw, s), f"libframe_ops_hip.so does not export {s}"
-    assert sorted(frame_lib.SYMBOLS) == syms
-    assert frame_lib.lib.frameops_abi_version() == frame_lib.ABI_VERSION
-    header = open(os.path.join(ROOT, "include", "frame_ops_hip.h")).read()
-    assert int(re.search(r"#define FRAMEOPS_ABI_VERSION (\d+)", header).group(1)) == frame_lib.ABI_VERSION
 
 
 def test_argument_errors_are_reported_without_a_device(frame_lib):

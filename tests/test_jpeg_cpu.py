@@ -9,11 +9,14 @@ import os
 import re
 import shutil
 import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_helpers
+from cabi_helpers import assert_binding_matches_header
 from conftest import ROOT, load_golden
 
 from memotr_amd.data import jpeg as J
@@ -249,32 +252,20 @@ def test_fallback_decodes_unsupported_streams_with_pillow(jpeg_lib, cases):
 
 
 # ------------------------------------------------------------------------------------ C ABI
-def header():
-    text = open(os.path.join(ROOT, "include", "jpeg_ops_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_library_exports_what_the_header_declares(jpeg_lib):
-    raw = ctypes.CDLL(jpeg_lib.LIB_PATH)
-    syms = sorted(set(re.findall(r"\b(jpegops_\w+)\s*\(", header())))
+    syms = assert_binding_matches_header(jpeg_lib, "jpeg_ops_hip.h", "jpegops", "JPEGOPS_ABI_VERSION")
     assert syms == ["jpegops_abi_version", "jpegops_decode_pixels_u8", "jpegops_entropy_decode",
                     "jpegops_entropy_decode_batch", "jpegops_last_error", "jpegops_parse_header",
                     "jpegops_planes_bytes"]
-    for s in syms:
-        assert hasattr(raw, s), f"libjpeg_ops_hip.so does not export {s}"
-    assert sorted(jpeg_lib.SYMBOLS) == syms
-    text = header()
-    for name, (argtypes, _) in jpeg_lib.SYMBOLS.items():
-        params = re.search(rf"\b{name}\s*\(([^)]*)\)", text).group(1).strip()
-        assert (0 if params == "void" else params.count(",") + 1) == len(argtypes), name
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", text).group(1))  # noqa: E731
-    assert define("JPEGOPS_ABI_VERSION") == jpeg_lib.ABI_VERSION == jpeg_lib.lib.jpegops_abi_version() == 1
+    define = partial(cabi_helpers.define, "jpeg_ops_hip.h")
+    assert jpeg_lib.ABI_VERSION == 1
     assert define("JPEGOPS_UNSUPPORTED") == jpeg_lib.UNSUPPORTED
     assert define("JPEGOPS_ERR_LEN") == jpeg_lib.ERR_LEN
     assert define("JPEGOPS_MAX_THREADS") == jpeg_lib.MAX_THREADS == 16
     assert define("JPEGOPS_QT_WORDS") == jpeg_lib.QT_WORDS == J.QT_WORDS
     assert (define("JPEGOPS_TILE_X"), define("JPEGOPS_TILE_Y")) == (jpeg_lib.TILE_X, jpeg_lib.TILE_Y)
-    fields = re.search(r"typedef struct jpegops_info \{(.*?)\}", text, flags=re.S).group(1)
+    fields = re.search(r"typedef struct jpegops_info \{(.*?)\}", cabi_helpers.header_text("jpeg_ops_hip.h"),
+                       flags=re.S).group(1)
     declared = [re.sub(r"\[\d+\]", "", f.strip()) for line in fields.split(";") if line.strip()
                 for f in line.strip().split(" ", 1)[1].split(",")]
     assert declared == [f[0] for f in jpeg_lib.Info._fields_]

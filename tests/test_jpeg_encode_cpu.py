@@ -10,11 +10,14 @@ import re
 import shutil
 import struct
 import subprocess
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+import cabi_helpers
+from cabi_helpers import assert_binding_matches_header
 from conftest import ROOT, load_golden
 
 from memotr_amd.data import jpeg as J
@@ -212,26 +215,13 @@ def test_a_short_buffer_returns_the_size_and_is_not_overrun(enc_lib, cases):
     assert buf[:len(want)].tobytes() == want and (buf[len(want):] == 0xA5).all()
 
 
-def header() -> str:
-    with open(os.path.join(ROOT, "include", "jpeg_enc_hip.h")) as f:
-        return f.read()
-
-
 def test_library_exports_what_the_header_declares(enc_lib):
-    raw = ctypes.CDLL(enc_lib.LIB_PATH)
-    text = header()
-    syms = sorted(set(re.findall(r"\b(jpegenc_\w+)\s*\(", text)))
+    syms = assert_binding_matches_header(enc_lib, "jpeg_enc_hip.h", "jpegenc", "JPEGENC_ABI_VERSION")
     assert syms == ["jpegenc_abi_version", "jpegenc_forward_u8", "jpegenc_geometry", "jpegenc_huffman_encode",
                     "jpegenc_huffman_encode_batch", "jpegenc_last_error", "jpegenc_planes_bytes",
                     "jpegenc_quant_tables"]
-    for s in syms:
-        assert hasattr(raw, s), f"libjpeg_enc_hip.so does not export {s}"
-    assert sorted(enc_lib.SYMBOLS) == syms
-    for name, (argtypes, _) in enc_lib.SYMBOLS.items():
-        params = re.search(rf"^[\w *]+\b{name}\s*\(([^)]*)\)", text, flags=re.M).group(1).strip()
-        assert (0 if params == "void" else params.count(",") + 1) == len(argtypes), name
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", text).group(1))  # noqa: E731
-    assert define("JPEGENC_ABI_VERSION") == enc_lib.ABI_VERSION == enc_lib.lib.jpegenc_abi_version() == 1
+    define = partial(cabi_helpers.define, "jpeg_enc_hip.h")
+    assert enc_lib.ABI_VERSION == 1
     assert define("JPEGENC_ERR_LEN") == enc_lib.ERR_LEN
     assert define("JPEGENC_MAX_THREADS") == enc_lib.MAX_THREADS == 16
     assert define("JPEGENC_QT_WORDS") == enc_lib.QT_WORDS == J.QT_WORDS

@@ -1,12 +1,10 @@
 """CPU: libtrack_motion_hip.so loads and exports exactly what include/track_motion_hip.h declares; argument
 validation is host-side and works without a device (nothing is launched here)."""
 import ctypes
-import os
-import re
 
 import pytest
 
-from conftest import ROOT
+from cabi_helpers import assert_binding_matches_header, assert_parameter_counts, define
 
 
 @pytest.fixture(scope="module")
@@ -17,34 +15,22 @@ def motion_lib():
     return _track_motion_lib
 
 
-def header():
-    text = open(os.path.join(ROOT, "include", "track_motion_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+HEADER = "track_motion_hip.h"
 
 
 def test_library_exports_every_declared_symbol(motion_lib):
-    raw = ctypes.CDLL(motion_lib.LIB_PATH)
-    syms = sorted(set(re.findall(r"\b(trackmotion_\w+)\s*\(", header())))
+    syms = assert_binding_matches_header(motion_lib, HEADER, "trackmotion", "TRACKMOTION_ABI_VERSION")
     assert syms == ["trackmotion_abi_version", "trackmotion_extrapolate", "trackmotion_last_error",
                     "trackmotion_observe", "trackmotion_register"]
-    for s in syms:
-        assert hasattr(raw, s), f"libtrack_motion_hip.so does not export {s}"
-    assert sorted(motion_lib.SYMBOLS) == syms
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", header()).group(1))  # noqa: E731
-    assert define("TRACKMOTION_ABI_VERSION") == motion_lib.ABI_VERSION == motion_lib.lib.trackmotion_abi_version()
     from memotr_amd.models import motion
-    assert define("TRACKMOTION_MAX_LENGTH") == motion_lib.MAX_LENGTH == motion.MAX_LENGTH == 16
-    assert define("TRACKMOTION_STATUS_NEGATIVE_ID") == motion_lib.STATUS_NEGATIVE_ID
-    assert define("TRACKMOTION_STATUS_ID_PAST_CAPACITY") == motion_lib.STATUS_ID_PAST_CAPACITY
-    assert define("TRACKMOTION_STATUS_BAD_LABEL") == motion_lib.STATUS_BAD_LABEL
+    assert define(HEADER, "TRACKMOTION_MAX_LENGTH") == motion_lib.MAX_LENGTH == motion.MAX_LENGTH == 16
+    assert define(HEADER, "TRACKMOTION_STATUS_NEGATIVE_ID") == motion_lib.STATUS_NEGATIVE_ID
+    assert define(HEADER, "TRACKMOTION_STATUS_ID_PAST_CAPACITY") == motion_lib.STATUS_ID_PAST_CAPACITY
+    assert define(HEADER, "TRACKMOTION_STATUS_BAD_LABEL") == motion_lib.STATUS_BAD_LABEL
 
 
 def test_declared_parameter_counts_match_the_binding(motion_lib):
-    text = header()
-    for name, (argtypes, _) in motion_lib.SYMBOLS.items():
-        params = re.search(rf"\b{name}\s*\(([^)]*)\)", text).group(1).strip()
-        n = 0 if params == "void" else params.count(",") + 1
-        assert n == len(argtypes), name
+    assert_parameter_counts(motion_lib, HEADER)
 
 
 def test_argument_errors_are_reported_without_a_device(motion_lib):

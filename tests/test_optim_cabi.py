@@ -1,12 +1,11 @@
 """CPU: libopt_ops_hip.so loads and exports exactly what include/opt_ops_hip.h declares; argument validation is
 host-side and works without a device (nothing is launched here)."""
 import ctypes
-import os
 import re
 
 import pytest
 
-from conftest import ROOT
+from cabi_helpers import assert_binding_matches_header, assert_parameter_counts, define, header_text
 
 
 @pytest.fixture(scope="module")
@@ -17,31 +16,20 @@ def opt_lib():
     return _opt_lib
 
 
-def header():
-    text = open(os.path.join(ROOT, "include", "opt_ops_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+HEADER = "opt_ops_hip.h"
 
 
 def test_library_exports_every_declared_symbol(opt_lib):
-    raw = ctypes.CDLL(opt_lib.LIB_PATH)
-    syms = sorted(set(re.findall(r"\b(optstep_\w+)\s*\(", header())))
+    syms = assert_binding_matches_header(opt_lib, HEADER, "optstep", "OPTSTEP_ABI_VERSION")
     assert syms == ["optstep_abi_version", "optstep_adamw", "optstep_last_error", "optstep_sumsq"]
-    for s in syms:
-        assert hasattr(raw, s), f"libopt_ops_hip.so does not export {s}"
-    assert sorted(opt_lib.SYMBOLS) == syms
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", header()).group(1))  # noqa: E731
-    assert define("OPTSTEP_ABI_VERSION") == opt_lib.ABI_VERSION == opt_lib.lib.optstep_abi_version()
-    assert define("OPTSTEP_CHUNK") == opt_lib.CHUNK
-    assert define("OPTSTEP_MAX_GROUPS") == opt_lib.MAX_GROUPS == 8
-    assert define("OPTSTEP_MAX_CHUNKS") == opt_lib.MAX_CHUNKS
+    assert define(HEADER, "OPTSTEP_CHUNK") == opt_lib.CHUNK
+    assert define(HEADER, "OPTSTEP_MAX_GROUPS") == opt_lib.MAX_GROUPS == 8
+    assert define(HEADER, "OPTSTEP_MAX_CHUNKS") == opt_lib.MAX_CHUNKS
 
 
 def test_declared_parameter_counts_and_record_layouts_match_the_binding(opt_lib):
-    text = header()
-    for name, (argtypes, _) in opt_lib.SYMBOLS.items():
-        params = re.search(rf"\b{name}\s*\(([^)]*)\)", text).group(1).strip()
-        n = 0 if params == "void" else params.count(",") + 1
-        assert n == len(argtypes), name
+    assert_parameter_counts(opt_lib, HEADER)
+    text = header_text(HEADER)
     # the records the tables are assembled in: field order and sizes as the header's structs
     fields = lambda struct: re.findall(r"(\w+)\s*[;,]", re.search(   # noqa: E731
         rf"typedef struct \{{([^}}]*)\}} {struct};", text).group(1))

@@ -2,14 +2,15 @@
 (tests/golden/track_draw_scene.npz) and against structural facts that follow from the definition; the palette is its
 integer formula; the font in the library is the font in Python; the C ABI is what the header declares."""
 import ctypes
-import os
-import re
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, load_golden
+import cabi_helpers
+from cabi_helpers import assert_binding_matches_header
+from conftest import load_golden
 from track_draw_cases import IDS, SIZES, frame, many, named_boxes
 
 from memotr_amd import render as R
@@ -180,19 +181,10 @@ def test_library_font_header_and_argument_codes(draw_lib):
     font = np.zeros(70, np.uint8)
     lib.trackdraw_font(font.ctypes.data)
     assert font.reshape(10, 7).tolist() == [list(g) for g in R.FONT]
-    with open(os.path.join(ROOT, "include", "track_draw_hip.h")) as f:
-        text = f.read()
-    syms = sorted(set(re.findall(r"\b(trackdraw_\w+)\s*\(", text)))
-    assert syms == sorted(draw_lib.SYMBOLS) == ["trackdraw_abi_version", "trackdraw_draw_u8", "trackdraw_font",
-                                                "trackdraw_last_error"]
-    raw = ctypes.CDLL(draw_lib.LIB_PATH)
-    for s in syms:
-        assert hasattr(raw, s)
-    for name, (argtypes, _) in draw_lib.SYMBOLS.items():
-        params = re.search(rf"^[\w *]+\b{name}\s*\(([^)]*)\)", text, flags=re.M).group(1).strip()
-        assert (0 if params == "void" else params.count(",") + 1) == len(argtypes), name
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", text).group(1))  # noqa: E731
-    assert define("TRACKDRAW_ABI_VERSION") == draw_lib.ABI_VERSION == lib.trackdraw_abi_version() == 1
+    syms = assert_binding_matches_header(draw_lib, "track_draw_hip.h", "trackdraw", "TRACKDRAW_ABI_VERSION")
+    assert syms == ["trackdraw_abi_version", "trackdraw_draw_u8", "trackdraw_font", "trackdraw_last_error"]
+    define = partial(cabi_helpers.define, "track_draw_hip.h")
+    assert draw_lib.ABI_VERSION == 1
     assert define("TRACKDRAW_ROW_WORDS") == draw_lib.ROW_WORDS == R.ROW_WORDS
     assert define("TRACKDRAW_MAX_GLYPHS") == draw_lib.MAX_GLYPHS == R.MAX_GLYPHS
     assert (define("TRACKDRAW_TILE_X"), define("TRACKDRAW_TILE_Y"), define("TRACKDRAW_CHUNK")) == \

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from cabi_helpers import assert_binding_matches_header
 from track_eval_helpers import SETS, check_results, check_tables, golden
 
 from memotr_amd import evaluation as E
@@ -177,20 +178,10 @@ def test_evaluator_rejects_what_trackeval_rejects():
 
 
 # ------------------------------------------------------------------------------------------------------- the C ABI
-def declared_symbols():
-    header = open(os.path.join(ROOT, "include", "track_eval_hip.h")).read()
-    return sorted(set(re.findall(r"\b(trackeval_\w+)\s*\(", header)))
-
-
 def test_library_exports_every_declared_symbol(track_eval_lib):
-    raw = ctypes.CDLL(track_eval_lib.LIB_PATH)
-    syms = declared_symbols()
+    syms = assert_binding_matches_header(track_eval_lib, "track_eval_hip.h", "trackeval", "TRACKEVAL_ABI_VERSION")
     assert len(syms) == 9
-    for s in syms:
-        assert hasattr(raw, s), f"libtrack_eval_hip.so does not export {s}"
-    assert sorted(track_eval_lib.SYMBOLS) == syms
     header = open(os.path.join(ROOT, "include", "track_eval_hip.h")).read()
-    assert int(re.search(r"#define TRACKEVAL_ABI_VERSION (\d+)", header).group(1)) == track_eval_lib.ABI_VERSION
     assert int(re.search(r"#define TRACKEVAL_MAX_DIM (\d+)", header).group(1)) == track_eval_lib.MAX_DIM == 2048
     assert int(re.search(r"#define TRACKEVAL_N_ALPHA (\d+)", header).group(1)) == track_eval_lib.N_ALPHA == len(E.ALPHAS)
     assert track_eval_lib.CLEAR_INTS == E.CLEAR_INTS[:8]

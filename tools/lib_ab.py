@@ -198,16 +198,13 @@ def bits_cases():
 
 
 def bits_main(args):
+    from memotr_amd._cabi import declare
     from memotr_amd._lib import SYMBOLS
     cases = bits_cases()
     libs = []
     for spec in args.libs:
         name, path = spec.split("=", 1)
-        lib = ctypes.CDLL(os.path.abspath(path))
-        for sym, (argtypes, restype) in SYMBOLS.items():
-            fn = getattr(lib, sym)
-            fn.argtypes, fn.restype = argtypes, restype
-        libs.append((name, lib))
+        libs.append((name, declare(ctypes.CDLL(os.path.abspath(path)), SYMBOLS)))
     runs = {}               # (library, pass) -> [(kernel, {output: tensor})]
     for name, lib in libs:
         for p in range(2):
