@@ -2,7 +2,9 @@
 
 Values transcribed from configs/train_dancetrack.yaml, train_mot17.yaml and train_bdd100k.yaml of the
 reference (flat UPPER_CASE keys, read by the ``build(config)`` functions exactly like the reference's).
-Only the keys the per-frame path and the train step read are kept; data-pipeline keys are out of scope.
+The three model functions keep only the keys the per-frame path and the train step read; ``data_config`` adds the
+data-pipeline keys (``data/datasets.py``, ``data/loader.py``) of the four shipped training configs, and ``load_yaml``
+reads a user's file in the reference's format.
 """
 from __future__ import annotations
 
@@ -43,4 +45,48 @@ def bdd100k_config(**overrides) -> dict:
     """configs/train_bdd100k.yaml: 8 classes, 720x1280 inputs, clips of up to 4 frames (:67), MISS_TOLERANCE 10 (:26)."""
     cfg = dancetrack_config(DATASET="BDD100K", SAMPLE_LENGTHS=[2, 3, 4], MISS_TOLERANCE=10)
     cfg.update(overrides)
+    return cfg
+
+
+_DATA_KEYS = {
+    # configs/train_dancetrack.yaml:45-56, 80-83 (keys the file leaves empty are None, as yaml reads them)
+    "DanceTrack": dict(DATA_ROOT=None, NUM_WORKERS=4, COCO_SIZE=False, OVERFLOW_BBOX=False, REVERSE_CLIP=0.0,
+                       SAMPLE_STEPS=[6, 10, 14], SAMPLE_LENGTHS=[2, 3, 4, 5], SAMPLE_MODES=["random_interval"],
+                       SAMPLE_INTERVALS=[10], USE_CROWDHUMAN=None, USE_MOTSYNTH=None, MOTSYNTH_RATE=None),
+    # configs/train_sportsmot.yaml:44-55, 79-82
+    "SportsMOT": dict(DATA_ROOT=None, NUM_WORKERS=4, COCO_SIZE=False, OVERFLOW_BBOX=False, REVERSE_CLIP=0.0,
+                      SAMPLE_STEPS=[10, 16, 22], SAMPLE_LENGTHS=[2, 3, 4, 5], SAMPLE_MODES=["random_interval"],
+                      SAMPLE_INTERVALS=[10], USE_CROWDHUMAN=None, USE_MOTSYNTH=None, MOTSYNTH_RATE=None),
+    # configs/train_mot17.yaml:44-55, 79-83
+    "MOT17": dict(DATA_ROOT=None, NUM_WORKERS=4, COCO_SIZE=True, OVERFLOW_BBOX=True, REVERSE_CLIP=0.0,
+                  SAMPLE_STEPS=[60, 100], SAMPLE_LENGTHS=[2, 3, 4], SAMPLE_MODES=["random_interval"],
+                  SAMPLE_INTERVALS=[10], SAMPLE_MOT17_JOIN=0, USE_CROWDHUMAN=True, USE_MOTSYNTH=None,
+                  MOTSYNTH_RATE=None),
+    # configs/train_bdd100k.yaml:39-42, 66-69 (the file has no augmentation keys: data/bdd100k.py fixes them)
+    "BDD100K": dict(DATA_ROOT=None, NUM_WORKERS=8, SAMPLE_STEPS=[6, 10], SAMPLE_LENGTHS=[2, 3, 4],
+                    SAMPLE_MODES=["random_interval"], SAMPLE_INTERVALS=[4, 4, 4]),
+}
+
+
+def data_config(dataset: str, **overrides) -> dict:
+    """The data-pipeline keys of the shipped training config for ``dataset`` ("DanceTrack", "SportsMOT", "MOT17",
+    "BDD100K"), with ``DATASET`` itself; to be merged over a model config:
+    ``dict(dancetrack_config(), **data_config("DanceTrack", DATA_ROOT="/data"))``.  NUM_WORKERS is transcribed and not
+    read: the clip loader has one producer thread and no worker processes."""
+    if dataset not in _DATA_KEYS:
+        raise ValueError(f"no shipped data config for dataset {dataset!r} (one of {sorted(_DATA_KEYS)})")
+    cfg = {k: (list(v) if isinstance(v, list) else v) for k, v in _DATA_KEYS[dataset].items()}
+    cfg["DATASET"] = dataset
+    cfg.update(overrides)
+    return cfg
+
+
+def load_yaml(path: str) -> dict:
+    """A training config in the reference's format: one flat mapping of UPPER_CASE keys (utils/utils.py:yaml_to_dict
+    there).  Needs PyYAML."""
+    import yaml
+    with open(path) as f:
+        cfg = yaml.safe_load(f)
+    if not isinstance(cfg, dict):
+        raise ValueError(f"{path}: a config is one mapping of keys to values, got {type(cfg).__name__}")
     return cfg

@@ -350,12 +350,14 @@ def _fallback(a: np.ndarray, device: torch.device, bgr: bool, error: Unsupported
 
 
 def decode_jpeg(data_or_path, device="cpu", bgr: bool = False, fallback: bool = True,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, staging: Optional[_Staging] = None) -> torch.Tensor:
     """One stream (bytes, a 1-D uint8 array or a path) -> (H, W, 3) uint8 on ``device``, RGB (``bgr=True``: B, G, R,
     ``cv2.imread``'s order).  CUDA: entropy stage into a pinned buffer, non-blocking upload and the two kernels on the
     current stream; nothing here waits for them.  ``out``: a (H, W, 3) uint8 CUDA tensor to write into, rows may be
-    pitched; bytes outside the pixels are left alone."""
+    pitched; bytes outside the pixels are left alone.  ``staging``: the pinned ring to use instead of the module's
+    (which is for ONE thread: a second decoding thread brings its own ``_Staging``)."""
     device = torch.device(device)
+    staging = _STAGING if staging is None else staging
     a = _as_bytes(data_or_path)
     try:
         info = parse_jpeg(a)
@@ -363,7 +365,7 @@ def decode_jpeg(data_or_path, device="cpu", bgr: bool = False, fallback: bool = 
             return torch.from_numpy(decode_coefficients_host(entropy_decode(a), bgr=bgr))
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        buf, slot = _STAGING.take(_frame_words(info))
+        buf, slot = staging.take(_frame_words(info))
         coefs = entropy_decode(a, pinned=buf)
     except UnsupportedJpeg as e:
         if not fallback:
@@ -374,7 +376,7 @@ def decode_jpeg(data_or_path, device="cpu", bgr: bool = False, fallback: bool = 
             return out
         return px
     frame = _device_stage(coefs.flat[None], coefs.info, 1, device, bgr, None if out is None else out[None])[0]
-    _STAGING.copied(slot, torch.cuda.current_stream(device).record_event())
+    staging.copied(slot, torch.cuda.current_stream(device).record_event())
     return frame
 
 
@@ -402,12 +404,13 @@ def _entropy_batch(streams: Sequence[np.ndarray], infos: Sequence[JpegInfo], hos
             _raise(status[i], f"frame {i}: {msg}")
 
 
-def decode_jpegs(items: Sequence, device="cpu", threads: int = 4, bgr: bool = False,
-                 fallback: bool = True) -> Union[torch.Tensor, List[torch.Tensor]]:
+def decode_jpegs(items: Sequence, device="cpu", threads: int = 4, bgr: bool = False, fallback: bool = True,
+                 staging: Optional[_Staging] = None) -> Union[torch.Tensor, List[torch.Tensor]]:
     """A clip.  Frames of one geometry: one batched entropy call on ``threads`` host threads (never sized by the
     machine's CPU count), one upload, one device stage, and a (T, H, W, 3) uint8 tensor.  Mixed geometries, or a
-    stream only Pillow reads: a list of (H, W, 3) tensors, frame by frame."""
+    stream only Pillow reads: a list of (H, W, 3) tensors, frame by frame.  ``staging``: as for ``decode_jpeg``."""
     device = torch.device(device)
+    staging = _STAGING if staging is None else staging
     streams = [_as_bytes(x) for x in items]
     if not streams:
         return []
@@ -418,7 +421,7 @@ def decode_jpegs(items: Sequence, device="cpu", threads: int = 4, bgr: bool = Fa
             raise
         infos = None
     if infos is None or any(f.geometry != infos[0].geometry for f in infos):
-        return [decode_jpeg(a, device, bgr=bgr, fallback=fallback) for a in streams]
+        return [decode_jpeg(a, device, bgr=bgr, fallback=fallback, staging=staging) for a in streams]
     info, T = infos[0], len(streams)
     words = _frame_words(info)
     if device.type != "cuda":
@@ -428,9 +431,9 @@ def decode_jpegs(items: Sequence, device="cpu", threads: int = 4, bgr: bool = Fa
                                           for i in range(T)]))
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    buf, slot = _STAGING.take(T * words)
+    buf, slot = staging.take(T * words)
     host = buf[:T * words].view(T, words)
     _entropy_batch(streams, infos, host, threads)
     frames = _device_stage(host, info, T, device, bgr)
-    _STAGING.copied(slot, torch.cuda.current_stream(device).record_event())
+    staging.copied(slot, torch.cuda.current_stream(device).record_event())
     return frames

@@ -2,7 +2,8 @@
 and ``engine.optimizer_step``.
 
 ``fit`` is ``train()`` without the data pipeline (``make_batches(epoch)`` yields collate-format batches) and without
-the logger: learning-rate schedule, the epoch policies (ONLY_TRAIN_QUERY_UPDATER_AFTER, the NO_GRAD_STEPS /
+the logger; ``train_from_config`` puts the data pipeline in front of it (``data.build_dataset``, ``data.ClipLoader``).
+In ``fit``, learning-rate schedule, the epoch policies (ONLY_TRAIN_QUERY_UPDATER_AFTER, the NO_GRAD_STEPS /
 NO_GRAD_FRAMES table), RESUME / RESUME_SCHEDULER and the checkpoint cadence are the reference's, line by line.
 ``train_one_epoch`` keeps the losses on the device and reads them every ``log_every`` iterations in one transfer: the
 reference's ``loss.item()`` per iteration is a host synchronisation per clip.
@@ -116,3 +117,35 @@ def fit(config: dict, model, criterion, make_batches: Callable[[int], Iterable[d
                 save_checkpoint(model=model, path=os.path.join(outputs_dir, f"checkpoint_{epoch}.pth"),
                                 states=states, optimizer=optimizer, scheduler=scheduler)
     return optimizer, scheduler, states
+
+
+def train_from_config(config: dict, device=None, *, prefetch: int = 2, decode_threads: int = 2, shuffle: bool = True,
+                      outputs_dir: Optional[str] = None, impl: Optional[str] = None, log_every: int = 100,
+                      on_log: Optional[Callable[[dict], None]] = None):
+    """train_engine.py:32-155 from a config alone: ``build_model``, ``build_criterion``, ``build_dataset`` on
+    config["DATA_ROOT"], a ``ClipLoader`` seeded with config["SEED"] and ``fit(..., loader.epoch, ...)``.  When
+    ``torch.distributed`` is initialised the loader takes this process's rank and the world size, and the model is
+    wrapped in ``DistributedDataParallel`` as ``train_bench.py`` wraps it.  ``device`` defaults to the model's.
+    Returns (model, optimizer, scheduler, states)."""
+    import torch.distributed as dist
+
+    from .data import ClipLoader, build_dataset
+    from .models import build_model
+    from .models.criterion import build as build_criterion
+    model = build_model(config)
+    if device is None:
+        device = next(model.parameters()).device
+    device = torch.device(device)
+    criterion = build_criterion(config)
+    rank, world_size = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() \
+        else (0, 1)
+    if world_size > 1:
+        from torch.nn.parallel import DistributedDataParallel as DDP
+        model = DDP(model, device_ids=[device.index] if device.type == "cuda" else None,
+                    find_unused_parameters=False, broadcast_buffers=False, gradient_as_bucket_view=True)
+    dataset = build_dataset(config, split="train")
+    loader = ClipLoader(dataset, device, seed=config["SEED"], shuffle=shuffle, rank=rank, world_size=world_size,
+                        prefetch=prefetch, decode_threads=decode_threads)
+    optimizer, scheduler, states = fit(config, model, criterion, loader.epoch, device=device, outputs_dir=outputs_dir,
+                                       impl=impl, log_every=log_every, on_log=on_log)
+    return model, optimizer, scheduler, states
