@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define CLIPOPS_ABI_VERSION 11
+#define CLIPOPS_ABI_VERSION 12
 
 int clipops_abi_version(void);
 const char *clipops_last_error(void);
@@ -226,6 +226,24 @@ int clipops_linear_fwd_f32(const float *x, const float *w, const float *bias, in
  * 637 us.  fp32 only: with 2-byte elements this tile shape loses to the two torch passes (546 vs 358 us, measured). */
 int clipops_relu_bwd_colsum_partial_f32(const float *g, const float *y, long rows, int cols, int chunk_rows, float *g2,
                                         float *partial, void *stream);
+
+/* ---- result rows of a tracked sequence, kept on the device (ABI 12) ----
+ * The reportable tracks of one frame (reference submit_engine.py:95-112: score and area filters, xyxy pixel boxes),
+ * appended to a table that stays on the device until the sequence ends.  For row i of the n live tracks, in float32
+ * with every operation rounded once:
+ *   s = max_k scores[i,k];  area = ((w * ori_w) * h) * ori_h;  kept when s > score_thresh and area > area_thresh
+ *   (both strict; a NaN score or area is dropped, as torch's max and > drop it);
+ *   kept rows store x1 = (cx - 0.5 w) ori_w, y1 = (cy - 0.5 h) ori_h, x2 = (cx + 0.5 w) ori_w, y2 = (cy + 0.5 h) ori_h
+ *   and s in rows_f (capacity,5), and frame, ids[i], labels[i] in rows_i (capacity,3).
+ * Kept rows keep the order of the input and start at row counters[0] as it was when the call began; afterwards
+ * counters[0] has grown by the number stored.  A row that would land at or past `capacity` is not stored but counted
+ * in counters[1]; nothing is written past the tables.  One 256-thread workgroup (n is tens to hundreds): ballot and
+ * population count inside a wavefront, wave totals through LDS, no atomics -- the same inputs give the same table.
+ * Calls on one table are issued on one stream.  n == 0 launches nothing.  Returns 1 for a bad argument (negative
+ * size, K < 1, null pointer with n > 0), 3 when the launch failed. */
+int clipops_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels, int n,
+                            int K, int64_t frame, float ori_w, float ori_h, float score_thresh, float area_thresh,
+                            float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from . import _cabi
 
 LIB_PATH = _cabi.lib_path("libclip_ops_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_int, c_long, c_float, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 
@@ -57,6 +57,8 @@ SYMBOLS = {
     "clipops_shift_relu_bf16": ([c_void_p, c_void_p, c_void_p, c_long, c_int, c_long, c_void_p], c_int),
     "clipops_refine_boxes_bwd_f32": ([c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p],
                                      c_int),
+    "clipops_result_rows_f32": ([c_void_p] * 4 + [c_int, c_int, ctypes.c_int64] + [c_float] * 4 + [c_void_p] * 3 +
+                                [c_int, c_void_p], c_int),
 }
 
 

@@ -1188,9 +1188,89 @@ __global__ __launch_bounds__(256) void focal_labels_kernel(const int64_t *__rest
     }
 }
 
+// ---- result rows of the submit path (ABI 12): the score / area filter and the pixel boxes of SequenceTracker._report,
+//      compacted onto the end of a device-resident table -- one launch per frame, no host read ----
+// one workgroup; rows in chunks of 256: a 64-bit ballot and the population count of the lower lanes place a row inside
+// its wavefront, the four wave totals go through LDS, `base` runs across chunks.  Both counters are read before
+// anything is written and written once, by one lane, with plain stores.  Every float operation rounds once.
+__global__ __launch_bounds__(256) void result_rows_kernel(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                          const int64_t *__restrict__ ids,
+                                                          const int64_t *__restrict__ labels, int n, int K, int64_t frame,
+                                                          float ori_w, float ori_h, float score_thresh, float area_thresh,
+                                                          float *__restrict__ rows_f, int64_t *__restrict__ rows_i,
+                                                          int32_t *__restrict__ counters, int capacity) {
+    __shared__ int wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stored0 = counters[0], dropped0 = counters[1];
+    int base = 0;                                   // rows kept by the chunks before this one
+    for (int c0 = 0; c0 < n; c0 += 256) {           // (n is uniform: every thread makes every trip)
+        const int i = c0 + (int)threadIdx.x;
+        bool keep = false;
+        float s = 0.f, cx = 0.f, cy = 0.f, w = 0.f, h = 0.f;
+        if (i < n) {
+            const float *sc = scores + (long)i * K;
+            s = sc[0];
+            for (int k = 1; k < K; ++k) {           // torch's max: a NaN wins and stays
+                const float v = sc[k];
+                if (v > s || v != v) s = v;
+            }
+            cx = boxes[4 * i], cy = boxes[4 * i + 1], w = boxes[4 * i + 2], h = boxes[4 * i + 3];
+            const float area = __fmul_rn(__fmul_rn(__fmul_rn(w, ori_w), h), ori_h);
+            keep = s > score_thresh && area > area_thresh;      // false for a NaN on either side
+        }
+        const unsigned long long m = __ballot(keep);
+        const int below = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int v = 0; v < 4; ++v) {
+            const int t = wave_total[v];
+            before += v < wave ? t : 0;
+            total += t;
+        }
+        if (keep) {
+            const long pos = (long)stored0 + base + before + below;
+            if (pos >= 0 && pos < capacity) {
+                const float hw = __fmul_rn(0.5f, w), hh = __fmul_rn(0.5f, h);
+                float *rf = rows_f + pos * 5;
+                rf[0] = __fmul_rn(__fsub_rn(cx, hw), ori_w);
+                rf[1] = __fmul_rn(__fsub_rn(cy, hh), ori_h);
+                rf[2] = __fmul_rn(__fadd_rn(cx, hw), ori_w);
+                rf[3] = __fmul_rn(__fadd_rn(cy, hh), ori_h);
+                rf[4] = s;
+                int64_t *ri = rows_i + pos * 3;
+                ri[0] = frame;
+                ri[1] = ids[i];
+                ri[2] = labels[i];
+            }
+        }
+        base += total;
+        __syncthreads();                            // wave_total is written again by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        const int room = stored0 < 0 ? 0 : (capacity > stored0 ? capacity - stored0 : 0);
+        const int stored = base < room ? base : room;
+        counters[0] = stored0 + stored;
+        counters[1] = dropped0 + (base - stored);
+    }
+}
+
 extern "C" {
 
 int clipops_abi_version(void) { return CLIPOPS_ABI_VERSION; }
+
+int clipops_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels, int n,
+                            int K, int64_t frame, float ori_w, float ori_h, float score_thresh, float area_thresh,
+                            float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream) {
+    if (n < 0 || capacity < 0) return fail(1, "clipops_result_rows_f32: negative size");
+    if (K < 1) return fail(1, "clipops_result_rows_f32: K < 1");
+    if (n == 0) { g_err[0] = 0; return 0; }
+    if (!boxes || !scores || !ids || !labels || !counters || (capacity > 0 && (!rows_f || !rows_i)))
+        return fail(1, "clipops_result_rows_f32: null pointer");
+    hipLaunchKernelGGL(result_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, boxes, scores, ids, labels, n, K,
+                       frame, ori_w, ori_h, score_thresh, area_thresh, rows_f, rows_i, counters, capacity);
+    return check_launch("result_rows_kernel") ? 3 : 0;
+}
 
 const char *clipops_last_error(void) { return g_err; }
 

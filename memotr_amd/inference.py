@@ -31,6 +31,12 @@ Huffman stage and the file a frame behind on one worker thread):
     with AnnotatedWriter("out/") as writer:
         for frame_idx, result in tracker.track_annotated(frames_or_paths, writer): ...
 
+Without a result on the host per frame (a submit run needs the rows of a sequence once; results.py, submit.py):
+
+    log = ResultLog(device)
+    n_frames = tracker.track_logged(frames_or_paths, log)              # one launch per frame instead of the read
+    lines = log.mot_lines("DanceTrack")
+
 ``use_motion=True`` (the reference's ``USE_MOTION``): after the query updater, the reference point of every track that
 is being missed is moved along its mean box velocity (models/motion.py: device state, one launch, no synchronisation).
 """
@@ -56,7 +62,8 @@ class SequenceTracker:
     def __init__(self, model, dataset_name: str = "DanceTrack", det_score_thresh: float = 0.7,
                  track_score_thresh: float = 0.6, result_score_thresh: float = 0.7, miss_tolerance: int = 5,
                  use_dab: bool = True, area_thresh: int = 100, raw_size=(800, 1536), use_motion: bool = False,
-                 motion_lambda: float = 0.5, motion_min_length: int = 3, motion_max_length: int = 5):
+                 motion_lambda: float = 0.5, motion_min_length: int = 3, motion_max_length: int = 5,
+                 side_stream=None):
         from .utils.host import respect_cpu_quota
         respect_cpu_quota()           # (a container's CFS quota vs torch's machine-sized thread pool: utils/host.py)
         self.model = model.eval()
@@ -76,7 +83,9 @@ class SequenceTracker:
                                                             use_dab=use_dab).to(self.device)]
         self._pending = None          # (image, encode result, event): the next frame's encode half, queued ahead
         self._slot = 0                # encode calls alternate between two graph slots (one may still be read)
-        self._side = None
+        self._side = side_stream      # the lookahead's stream; None: one of its own, made when first needed.  (Trackers
+        #                               made one after another can share one: which hardware queue a new stream lands on
+        #                               decides whether the lookahead overlaps at all -- profiles/submit_log.md)
         self.raw_size = raw_size      # step_raw: (short side, longest long side) of the resized frame; the reference's
         self._staging = [None, None]  # step_raw: two pinned upload buffers, each with the event of its last copy
         self._staging_i = 0
@@ -187,6 +196,12 @@ class SequenceTracker:
         turned into the padded normalised batch by one kernel (data/frames.py), then takes the encode path of ``step``
         (same slot alternation).  ``next_frame_u8``: the frame the next call will pass (the same object, unchanged until
         then); its upload, kernel and encode half are queued on the side stream as ``_prefetch`` does for ``step``."""
+        ori_h, ori_w = self._advance_raw(frame_u8, next_frame_u8, bgr=bgr)
+        return self._report(self.tracks[0], ori_h, ori_w)
+
+    @torch.no_grad()
+    def _advance_raw(self, frame_u8, next_frame_u8=None, *, bgr: bool = False):
+        """``step_raw`` up to the report: ``self.tracks`` are this frame's; returns ``(ori_h, ori_w)``."""
         ori_h, ori_w = int(frame_u8.shape[0]), int(frame_u8.shape[1])
         pending, self._pending = self._pending, None
         if pending is not None:
@@ -199,7 +214,7 @@ class SequenceTracker:
         self.tracks = self.core.postprocess_single_frame(previous, new, None)
         if self.use_motion:
             self._extrapolate_missed()
-        return self._report(self.tracks[0], ori_h, ori_w)
+        return ori_h, ori_w
 
     def track(self, frames, *, bgr: bool = False):
         """Generator over an iterable of uint8 frames: yields ``(frame_idx, result)``, one frame of lookahead."""
@@ -222,11 +237,13 @@ class SequenceTracker:
         for idx, _, result in self._track_jpeg_frames(files_or_bytes, bgr):
             yield idx, result
 
-    def _track_jpeg_frames(self, files_or_bytes, bgr: bool):
-        """The loop of ``track_jpeg``; yields ``(frame_idx, frame, result)`` with the decoded frame on the device."""
+    def _track_jpeg_frames(self, files_or_bytes, bgr: bool, step=None):
+        """The loop of ``track_jpeg``; yields ``(frame_idx, frame, result)`` with the decoded frame on the device.
+        ``step``: what is called per frame in place of ``step_raw`` (``track_logged``: ``_advance_raw``)."""
+        step = self.step_raw if step is None else step
         if self.device.type != "cuda":
             from .data.jpeg import decode_jpeg
-            yield from self._track_frames((decode_jpeg(x, "cpu", bgr=bgr) for x in files_or_bytes), bgr)
+            yield from self._track_frames((decode_jpeg(x, "cpu", bgr=bgr) for x in files_or_bytes), bgr, step)
             return
         from concurrent.futures import ThreadPoolExecutor
         from .data import jpeg as J
@@ -264,13 +281,14 @@ class SequenceTracker:
                 if job is not None:
                     decoded, job = job.result(), ahead()
                     nxt = pixels(decoded, self._side)
-                yield idx, cur, self.step_raw(cur, nxt, bgr=bgr)
+                yield idx, cur, step(cur, nxt, bgr=bgr)
                 cur, idx = nxt, idx + 1
 
-    def _track_frames(self, frames, bgr: bool):
+    def _track_frames(self, frames, bgr: bool, step=None):
         """``track`` that keeps hold of the device copy: yields ``(frame_idx, frame on the device, result)``.  The
         upload ``step_raw`` would make is made here, on the stream it would be made on (this frame's on the current
         stream, the next frame's on the side stream), and ``step_raw`` is handed the device tensor: one upload."""
+        step = self.step_raw if step is None else step
         cuda = self.device.type == "cuda"
         if cuda and self._side is None:
             self._side = torch.cuda.Stream(self.device)
@@ -290,7 +308,7 @@ class SequenceTracker:
         while cur is not None:
             nxt = next(it, done)
             nxt = None if nxt is done else upload(nxt, self._side)
-            yield idx, cur, self.step_raw(cur, nxt, bgr=bgr)
+            yield idx, cur, step(cur, nxt, bgr=bgr)
             cur, idx = nxt, idx + 1
 
     def track_annotated(self, source, writer, *, bgr: bool = False):
@@ -313,6 +331,39 @@ class SequenceTracker:
         for idx, frame, result in frames:
             writer.add(idx, frame, result, bgr=bgr)
             yield idx, result
+
+    def track_logged(self, source, log, *, bgr: bool = False) -> int:
+        """``track`` / ``track_jpeg`` (``source`` as for ``track_annotated``) with the reportable rows of every frame
+        appended to ``log`` (results.ResultLog) on the device instead of being brought to the host: one launch per frame
+        in place of ``_report``'s packed copy, event wait and host filter.  Read them once, after the sequence, with
+        ``log.read()`` / ``log.mot_lines`` / ``log.bdd_frames``.  Returns the number of frames."""
+        import itertools
+        import os
+        it = iter(source)
+        done = object()
+        first = next(it, done)
+        if first is done:
+            return 0
+
+        def append(idx, ori_h, ori_w):
+            t = self.tracks[0]
+            log.append(t.boxes, t.scores, t.ids, t.labels, idx, ori_h, ori_w, self.result_score_thresh,
+                       self.area_thresh)
+
+        stream_like = isinstance(first, (str, bytes, bytearray, memoryview, os.PathLike)) or \
+            (hasattr(first, "ndim") and first.ndim == 1)
+        if stream_like:
+            n = 0
+            for idx, _, size in self._track_jpeg_frames(itertools.chain([first], it), bgr, step=self._advance_raw):
+                append(idx, *size)
+                n = idx + 1
+            return n
+        cur, idx = first, 0                     # the loop of ``track``
+        while cur is not done:
+            nxt = next(it, done)
+            append(idx, *self._advance_raw(cur, None if nxt is done else nxt, bgr=bgr))
+            cur, idx = nxt, idx + 1
+        return idx
 
     def _upload(self, frame_u8) -> torch.Tensor:
         """The frame on the device, copied on the current stream.  Pageable host memory goes through one of two pinned

@@ -1,0 +1,194 @@
+"""The result rows of a tracked sequence, kept on the device until the sequence ends.
+
+``SequenceTracker._report`` brings the reportable tracks of every frame to the host: a packed copy through a pinned
+buffer and an event wait per frame.  A submit run needs none of them per frame -- it needs the rows of the whole
+sequence once.  ``ResultLog`` is that table: ``append`` is one launch of ``clipops_result_rows_f32``
+(include/clip_ops_hip.h: score and area filter, xyxy pixel boxes, ballot compaction onto the end of the table),
+``read`` one synchronisation and one copy.
+
+    log = ResultLog(device)
+    n_frames = tracker.track_logged(paths, log)
+    lines = log.mot_lines("DanceTrack")          # what tracker.mot_lines gives frame by frame
+    log.reset()                                   # next sequence
+
+On CPU tensors ``append`` runs ``host_rows``, the torch statement the kernel is held to (tests/test_result_log_gpu.py).
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple
+
+import numpy as np
+import torch
+
+ROW_F, ROW_I = 5, 3           # x1, y1, x2, y2, score | frame, id, label
+
+
+class Rows(NamedTuple):
+    frames: np.ndarray        # (m,) int64, 0-based
+    ids: np.ndarray           # (m,) int64
+    labels: np.ndarray        # (m,) int64
+    boxes_xyxy: np.ndarray    # (m, 4) float32, pixels of the original image
+    scores: np.ndarray        # (m,) float32
+
+
+def host_rows(boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labels: torch.Tensor, frame_idx: int,
+              ori_h, ori_w, score_thresh: float, area_thresh: float):
+    """``_report``'s filter and boxes in float32 (submit_engine.py:95-112): ``(rows_f (m,5), rows_i (m,3))`` of the
+    kept rows in input order.  Thresholds and image sizes meet the float32 tensors as Python scalars, so torch rounds
+    them to float32 first."""
+    n = boxes.shape[0]
+    if n == 0:
+        return boxes.new_zeros((0, ROW_F), dtype=torch.float32), ids.new_zeros((0, ROW_I), dtype=torch.int64)
+    boxes, scores = boxes.float(), scores.float().reshape(n, -1)
+    s = torch.max(scores, dim=-1).values
+    area = boxes[:, 2] * float(ori_w) * boxes[:, 3] * float(ori_h)
+    keep = (s > score_thresh) & (area > area_thresh)
+    b, half_w, half_h = boxes[keep], 0.5 * boxes[keep][:, 2], 0.5 * boxes[keep][:, 3]
+    rows_f = torch.stack(((b[:, 0] - half_w) * float(ori_w), (b[:, 1] - half_h) * float(ori_h),
+                          (b[:, 0] + half_w) * float(ori_w), (b[:, 1] + half_h) * float(ori_h), s[keep]), dim=1)
+    rows_i = torch.stack((torch.full_like(ids[keep], int(frame_idx)), ids[keep], labels[keep]), dim=1)
+    return rows_f, rows_i
+
+
+class ResultLog:
+    """``rows_f`` (capacity, 5) float32, ``rows_i`` (capacity, 3) int64 and ``counters`` (2,) int32 (rows stored, rows
+    dropped for lack of room) on ``device``.  All calls on one log are made on one stream."""
+
+    def __init__(self, device, capacity: int = 4096):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity = max(1, int(capacity))
+        self.rows_f = torch.empty((self.capacity, ROW_F), dtype=torch.float32, device=self.device)
+        self.rows_i = torch.empty((self.capacity, ROW_I), dtype=torch.int64, device=self.device)
+        self.counters = torch.zeros((2,), dtype=torch.int32, device=self.device)
+        self._bound = 0           # the rows appended can be no more than the rows offered: known without a read
+        self._rows = None         # the last read, until the next append / reset
+
+    # ------------------------------------------------------------------ device side
+    def _grow(self, needed: int) -> None:
+        """Larger tables and a stream-ordered device copy of the part that may be in use."""
+        capacity = max(2 * self.capacity, needed)
+        rows_f = torch.empty((capacity, ROW_F), dtype=torch.float32, device=self.device)
+        rows_i = torch.empty((capacity, ROW_I), dtype=torch.int64, device=self.device)
+        rows_f[:self._bound].copy_(self.rows_f[:self._bound])
+        rows_i[:self._bound].copy_(self.rows_i[:self._bound])
+        if self.device.type == "cuda":        # the old tables are read by that copy on this stream
+            stream = torch.cuda.current_stream(self.device)
+            self.rows_f.record_stream(stream)
+            self.rows_i.record_stream(stream)
+        self.rows_f, self.rows_i, self.capacity = rows_f, rows_i, capacity
+
+    @torch.no_grad()
+    def append(self, boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labels: torch.Tensor,
+               frame_idx: int, ori_h, ori_w, score_thresh: float, area_thresh: float) -> None:
+        """The reportable rows of one frame's live tracks (``boxes`` (n,4) cxcywh normalised, ``scores`` (n,K) or (n,),
+        ``ids`` / ``labels`` (n,)) behind the rows already there.  Nothing is read back."""
+        n = int(boxes.shape[0])
+        if n == 0:
+            return
+        if boxes.device != self.device:
+            raise ValueError(f"tracks on {boxes.device}, result log on {self.device}")
+        self._rows = None
+        if self._bound + n > self.capacity:
+            self._grow(self._bound + n)
+        if self.device.type != "cuda":
+            rows_f, rows_i = host_rows(boxes, scores, ids, labels, frame_idx, ori_h, ori_w, score_thresh, area_thresh)
+            at, m = int(self.counters[0]), rows_f.shape[0]
+            self.rows_f[at:at + m], self.rows_i[at:at + m] = rows_f, rows_i
+            self.counters[0] += m
+            self._bound += n
+            return
+        from . import _clip_lib as L      # no substitute: a missing library is an error
+        boxes = boxes.detach().float().contiguous()
+        scores = scores.detach().float().reshape(n, -1).contiguous()
+        ids, labels = ids.long().contiguous(), labels.long().contiguous()
+        L.check(L.lib.clipops_result_rows_f32(
+            boxes.data_ptr(), scores.data_ptr(), ids.data_ptr(), labels.data_ptr(), n, scores.shape[1], int(frame_idx),
+            float(ori_w), float(ori_h), float(score_thresh), float(area_thresh), self.rows_f.data_ptr(),
+            self.rows_i.data_ptr(), self.counters.data_ptr(), self.capacity,
+            torch.cuda.current_stream(self.device).cuda_stream), "clipops_result_rows_f32")
+        self._bound += n
+
+    def reset(self) -> None:
+        """Empty the log for the next sequence (stream-ordered; the tables keep their size)."""
+        self.counters.zero_()
+        self._bound, self._rows = 0, None
+
+    # ------------------------------------------------------------------ host side
+    def read(self) -> Rows:
+        """The rows on the host: one packed copy through a pinned buffer and one event wait."""
+        if self._rows is not None:
+            return self._rows
+        b = self._bound
+        if self.device.type == "cuda":
+            packed = torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
+                                self.rows_f[:b].reshape(-1).view(torch.uint8)))
+            host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            done.synchronize()
+            raw = host.numpy()
+            counters = raw[:8].view(np.int32)
+            rows_i = raw[8:8 + b * ROW_I * 8].view(np.int64).reshape(b, ROW_I)
+            rows_f = raw[8 + b * ROW_I * 8:].view(np.float32).reshape(b, ROW_F)
+        else:
+            counters, rows_i, rows_f = self.counters.numpy(), self.rows_i[:b].numpy(), self.rows_f[:b].numpy()
+        stored, dropped = int(counters[0]), int(counters[1])
+        if dropped != 0:
+            raise RuntimeError(f"result log: {dropped} rows found no room in a table of {self.capacity}")
+        if stored > b:
+            raise RuntimeError(f"result log: {stored} rows stored, {b} offered (counters written from elsewhere?)")
+        rows_i, rows_f = rows_i[:stored], rows_f[:stored]
+        self._rows = Rows(rows_i[:, 0].copy(), rows_i[:, 1].copy(), rows_i[:, 2].copy(),
+                          np.ascontiguousarray(rows_f[:, :4]), rows_f[:, 4].copy())
+        return self._rows
+
+    def __len__(self) -> int:
+        return len(self.read().frames)
+
+    def mot_lines(self, dataset_name: str) -> List[str]:
+        """``SequenceTracker.mot_lines`` of every frame, in order: ``frame+1,id,x1,y1,w,h,1,-1,-1,-1`` with ``w`` and
+        ``h`` formed in Python floats from the float32 corners."""
+        from .inference import MOT_STYLE
+        if dataset_name not in MOT_STYLE:
+            raise ValueError(f"{dataset_name} dataset is not supported for submit process.")
+        r = self.read()
+        return [f"{f + 1},{tid},{x1},{y1},{x2 - x1},{y2 - y1},1,-1,-1,-1\n"
+                for f, tid, (x1, y1, x2, y2) in zip(r.frames.tolist(), r.ids.tolist(), r.boxes_xyxy.tolist())]
+
+    def _by_frame(self):
+        """``{frame: slice of the rows}``: the rows of a frame are adjacent, frames ascend."""
+        frames = self.read().frames
+        starts = np.flatnonzero(np.diff(frames, prepend=-1))
+        ends = list(starts[1:]) + [len(frames)]
+        return {int(frames[a]): slice(int(a), int(e)) for a, e in zip(starts, ends)}
+
+    def bdd_frames(self, image_paths) -> List[dict]:
+        """``SequenceTracker.bdd_frame_result`` of every frame of the sequence, frames without a row included."""
+        from .inference import BDD_CLS2LABEL
+        r, where = self.read(), self._by_frame()
+        out = []
+        for idx, img_path in enumerate(image_paths):
+            name = str(img_path).split("/")[-1]
+            sl = where.get(idx, slice(0, 0))
+            labels = [{"id": str(tid), "category": BDD_CLS2LABEL[lab + 1],
+                       "box2d": {"x1": x1, "y1": y1, "x2": x2, "y2": y2}}
+                      for tid, lab, (x1, y1, x2, y2) in zip(r.ids[sl].tolist(), r.labels[sl].tolist(),
+                                                            r.boxes_xyxy[sl].tolist())]
+            out.append({"name": name, "videoName": name[:-12], "frameIndex": idx, "labels": labels})
+        return out
+
+    def add_to(self, evaluator, seq: str, n_frames: int = None) -> None:
+        """Feed a ``TrackingEvaluator`` what ``add_frame`` would have been given frame by frame: 1-based frames, xywh
+        boxes as the doubles ``mot_lines`` prints.  ``n_frames``: frames 0 .. n_frames - 1 are all added (empty ones
+        too, as ``add_frame`` adds them); default: up to the last frame with a row."""
+        r, where = self.read(), self._by_frame()
+        if n_frames is None:
+            n_frames = max(where) + 1 if where else 0
+        for idx in range(n_frames):
+            sl = where.get(idx, slice(0, 0))
+            boxes = [[x1, y1, x2 - x1, y2 - y1] for x1, y1, x2, y2 in r.boxes_xyxy[sl].tolist()]
+            evaluator.add_tracker_rows(seq, idx + 1, np.asarray(r.ids[sl].tolist(), np.int64),
+                                       np.asarray(boxes, np.float64).reshape(-1, 4))

@@ -1,0 +1,145 @@
+"""The submit engine: a checkpoint and a dataset split in, one result file per sequence out (the reference's
+``submit_engine.py:187-252`` and the ``Submitter`` it drives).
+
+    files = submit(dict(SUBMIT_DIR="outputs/dancetrack", SUBMIT_MODEL="checkpoint_19.pth", SUBMIT_DATA_SPLIT="val",
+                        DATA_ROOT="/data", DET_SCORE_THRESH=0.5, TRACK_SCORE_THRESH=0.5, RESULT_SCORE_THRESH=0.5,
+                        MISS_TOLERANCE=30, USE_MOTION=False))
+    # outputs/dancetrack/val/tracker/<seq>.txt      (BDD100K: <seq>.json)
+
+Every sequence is tracked by a fresh ``SequenceTracker`` through ``track_logged``: the result rows stay in one reused
+device-resident ``ResultLog`` and are read once, when the sequence ends (results.py).  With ``torch.distributed``
+initialised each rank takes every ``world_size``-th sequence of the sorted listing; there is no DistributedDataParallel
+wrap, since inference needs no collective.
+"""
+from __future__ import annotations
+
+import json
+import os
+from typing import Callable, List, Optional
+
+import torch
+
+from .results import ResultLog
+
+
+def split_dir(data_root: str, dataset: str, split: str) -> str:
+    """Where the sequences of ``split`` lie (submit_engine.py:217-222)."""
+    if dataset in ("DanceTrack", "SportsMOT"):
+        return os.path.join(data_root, dataset, split)
+    if dataset == "BDD100K":
+        return os.path.join(data_root, dataset, "images", "track", split)
+    return os.path.join(data_root, dataset, "images", split)
+
+
+def sequence_names(directory: str, rank: int = 0, world_size: int = 1) -> List[str]:
+    """This rank's share of the sequences: every ``world_size``-th name of the SORTED listing, from ``rank`` (the
+    reference shards ``os.listdir``'s order, which need not agree between processes)."""
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} outside 0 .. {world_size - 1}")
+    return sorted(os.listdir(directory))[rank::world_size]
+
+
+def sequence_frames(dataset: str, seq_dir: str) -> List[str]:
+    """The frames of a sequence in order (the reference's data/seq_dataset.py:11-19): sorted names containing ``jpg`` or
+    ``png``, under ``img1/`` except for BDD100K."""
+    image_dir = seq_dir if dataset == "BDD100K" else os.path.join(seq_dir, "img1")
+    return [os.path.join(image_dir, n) for n in sorted(os.listdir(image_dir)) if "jpg" in n or "png" in n]
+
+
+def _is_jpeg(path: str) -> bool:
+    with open(path, "rb") as f:
+        return f.read(2) == b"\xff\xd8"
+
+
+def _pixels(paths):
+    """Frames as (H, W, 3) uint8 RGB arrays, decoded on the host: JPEG by the package's decoder (the pixels the device
+    stage gives), anything else by Pillow -- the JPEG path's own Pillow fallback takes JPEG streams only."""
+    import numpy as np
+    from PIL import Image
+
+    from .data.jpeg import decode_jpeg
+    for p in paths:
+        if _is_jpeg(p):
+            yield decode_jpeg(p, "cpu")
+        else:
+            with Image.open(p) as im:
+                yield torch.from_numpy(np.array(im.convert("RGB"), order="C"))
+
+
+def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog) -> str:
+    """Track the sequence in ``seq_dir`` with a fresh tracker from ``tracker_factory()`` and write
+    ``<outputs_dir>/tracker/<seq>.txt`` (BDD100K: ``<seq>.json``) whole, replacing an older file.  ``log`` is emptied
+    first and holds the sequence's rows afterwards.  Returns the file's path."""
+    seq = os.path.basename(os.path.normpath(seq_dir))
+    paths = sequence_frames(dataset, seq_dir)
+    tracker = tracker_factory()
+    log.reset()
+    source = paths if all(_is_jpeg(p) for p in paths) else _pixels(paths)
+    n_frames = tracker.track_logged(source, log)
+    assert n_frames == len(paths)
+    predict_dir = os.path.join(outputs_dir, "tracker")
+    os.makedirs(predict_dir, exist_ok=True)
+    if dataset == "BDD100K":
+        out = os.path.join(predict_dir, seq + ".json")
+        with open(out, "w", encoding="utf-8") as f:
+            json.dump(log.bdd_frames(paths), f)
+    else:
+        out = os.path.join(predict_dir, seq + ".txt")
+        text = "".join(log.mot_lines(dataset))
+        with open(out, "w") as f:
+            f.write(text)
+    return out
+
+
+def load_model(train_config: dict, checkpoint: str):
+    """``build_model(train_config)`` with the weights of ``checkpoint`` -- loaded by every rank: without a
+    DistributedDataParallel wrap there is no broadcast to rely on."""
+    from .models import build_model
+    model = build_model(train_config)
+    model.load_state_dict(torch.load(checkpoint, map_location="cpu")["model"])
+    return model
+
+
+def _rank_and_world():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
+           tracker_options: Optional[dict] = None) -> List[str]:
+    """submit_engine.py:187-252.  ``config``: SUBMIT_DIR, SUBMIT_MODEL, SUBMIT_DATA_SPLIT, DATA_ROOT and the inference
+    thresholds (DET_SCORE_THRESH, TRACK_SCORE_THRESH, RESULT_SCORE_THRESH, MISS_TOLERANCE, USE_MOTION and the MOTION_*
+    keys).  ``train_config`` (DATASET, USE_DAB and the model's keys) defaults to ``<SUBMIT_DIR>/train/config.yaml``;
+    ``model`` defaults to ``load_model(train_config, <SUBMIT_DIR>/<SUBMIT_MODEL>)``.  ``tracker_options``: further
+    ``SequenceTracker`` arguments (``raw_size``, ``area_thresh``) for every sequence's tracker.  Returns the files this
+    rank wrote, in sequence order."""
+    from .inference import SequenceTracker
+    for key in ("SUBMIT_DIR", "SUBMIT_DATA_SPLIT", "DATA_ROOT"):
+        if config.get(key) is None:
+            raise ValueError(f"{key} must not be None for the submit process")
+    if train_config is None:
+        from .configs import load_yaml
+        train_config = load_yaml(os.path.join(config["SUBMIT_DIR"], "train", "config.yaml"))
+    dataset, split = train_config["DATASET"], config["SUBMIT_DATA_SPLIT"]
+    outputs_dir = os.path.join(config["SUBMIT_DIR"], split)
+    if model is None:
+        if config.get("SUBMIT_MODEL") is None:
+            raise ValueError("SUBMIT_MODEL must not be None for the submit process")
+        model = load_model(train_config, os.path.join(config["SUBMIT_DIR"], config["SUBMIT_MODEL"]))
+    device = next(model.parameters()).device
+    options = dict(
+        dataset_name=dataset, use_dab=train_config["USE_DAB"], det_score_thresh=config["DET_SCORE_THRESH"],
+        track_score_thresh=config["TRACK_SCORE_THRESH"], result_score_thresh=config["RESULT_SCORE_THRESH"],
+        miss_tolerance=config["MISS_TOLERANCE"], use_motion=bool(config.get("USE_MOTION", False)),
+        motion_lambda=config.get("MOTION_LAMBDA", 0.5), motion_min_length=config.get("MOTION_MIN_LENGTH", 3),
+        motion_max_length=config.get("MOTION_MAX_LENGTH", 5))
+    if device.type == "cuda":       # one lookahead stream for the run, not one per sequence (profiles/submit_log.md)
+        options["side_stream"] = torch.cuda.Stream(device)
+    options.update(tracker_options or {})
+    directory = split_dir(config["DATA_ROOT"], dataset, split)
+    log = ResultLog(device)
+    return [submit_sequence(lambda: SequenceTracker(model, **options), dataset,
+                            os.path.join(directory, seq), outputs_dir, log)
+            for seq in sequence_names(directory, *_rank_and_world())]
