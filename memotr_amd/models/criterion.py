@@ -165,6 +165,8 @@ class ClipCriterion:
         else:
             total = max(host[0], 1.0)
             per_frame = [max(c, 1.0) for c in host[1:]]
+        # (kept for log_components: the all-reduced vector under torch.distributed, else nothing -- the host has them)
+        self._counts = counts if is_distributed() else None
         loss = {k: v / total for k, v in self.loss.items()}
         log = {}
         if with_log:
@@ -174,6 +176,28 @@ class ClipCriterion:
                         log[k] = (float(v) / n, 1)
                         break
         return loss, log
+
+    def log_components(self) -> Tuple[List[str], torch.Tensor]:
+        """The clip's log values as ``get_mean_by_n_gts(with_log=True)`` normalises them, WITHOUT reading them: the names
+        (``frame{i}_box_l1_loss``, ... in the order the frames were processed) and one float32 device vector of
+        value / max(frame's mean ground-truth count, 1).  Call after ``get_mean_by_n_gts``: under torch.distributed the
+        counts are the ones its all-reduce left on the device; a single process uploads its host counts (pinned, queued
+        like a kernel).  One stack and one division per clip; the quotient is float32 here and float64 there."""
+        names = list(self.log)
+        if not names:
+            return names, torch.zeros((0,), device=self.device)
+        n_frames = len(self.n_gts)
+        frame_of = [next(i for i in range(n_frames) if f"frame{i}" in k) for k in names]    # with_log=True's rule
+        values = torch.stack([self.log[k] for k in names])
+        counts = self.__dict__.get("_counts")
+        if counts is not None:
+            half = _MAX_CLIP_FRAMES + 1
+            have = torch.clamp(counts[half + 1:half + 1 + n_frames], min=1)
+            per_frame = torch.clamp(counts[1:1 + n_frames] / have, min=1)
+            index = self._constant(("log_frames", tuple(frame_of)), frame_of, torch.long, values.device)
+            return names, values / per_frame.index_select(0, index)
+        divisors = upload([max(float(self.n_gts[i]), 1.0) for i in frame_of], values.dtype, values.device)
+        return names, values / divisors
 
     # ------------------------------------------------------------------ one frame
     def process_single_frame(self, model_outputs: dict, tracked_instances: List[TrackInstances], frame_idx: int):
