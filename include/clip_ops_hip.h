@@ -106,6 +106,17 @@ int clipops_refine_boxes_fwd_f32(const float *delta, const float *ref, long n, f
 int clipops_refine_boxes_bwd_f32(const float *out, const float *ref, const float *grad_out, long n, float eps,
                                  float *grad_delta, float *grad_ref, void *stream);
 
+/* Layer 0 of the Deformable-DETR variant (USE_DAB: False), both boxes from one `delta`; n_rows rows of four:
+ *   out_head[r,c] = sigmoid(delta[r,c] + inverse_sigmoid(ref[r,c]))          -- the model's box head, 4-d reference
+ *   out_dec[r,c]  = out_head[r,c] for c < 2, sigmoid(delta[r,c]) for c >= 2  -- the decoder's box, 2-d reference
+ * out_head is bit-equal to clipops_refine_boxes_fwd_f32(delta, ref); out_dec's last two columns are bit-equal to
+ * clipops_refine_boxes_fwd_f32(delta, 0.5) (inverse_sigmoid(0.5) is exactly 0).  The backward is
+ * clipops_refine_boxes_bwd_f32 on out_head: out_dec is only ever used detached.  The outputs must not alias.
+ * (Added without a new CLIPOPS_ABI_VERSION: no existing entry point changed, and a library built before it is
+ *  caught twice -- the source hash of the build rebuilds it, and binding the symbol table fails on the missing name.) */
+int clipops_refine_boxes_split_fwd_f32(const float *delta, const float *ref, long n_rows, float eps,
+                                       float *out_head, float *out_dec, void *stream);
+
 /* Column sums of a small row-major matrix: out[c] = sum_r x[r*cols + c] -- the bias gradient of a Linear over a few
  * hundred query rows.  torch's generic reduction takes 12-17 us for 310 x 256 .. 2048 on MI355X (one of ~400 such calls
  * per train step); this one tiles 32 columns x 8 row lanes per workgroup and sums in a fixed order.  All column-sum

@@ -57,6 +57,7 @@ SYMBOLS = {
     "clipops_shift_relu_bf16": ([c_void_p, c_void_p, c_void_p, c_long, c_int, c_long, c_void_p], c_int),
     "clipops_refine_boxes_bwd_f32": ([c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p],
                                      c_int),
+    "clipops_refine_boxes_split_fwd_f32": ([c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p], c_int),
     "clipops_result_rows_f32": ([c_void_p] * 4 + [c_int, c_int, ctypes.c_int64] + [c_float] * 4 + [c_void_p] * 3 +
                                 [c_int, c_void_p], c_int),
 }

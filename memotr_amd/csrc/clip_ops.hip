@@ -340,6 +340,43 @@ __global__ __launch_bounds__(256) void refine_boxes_fwd_kernel(const float *__re
         out[i] = sigmoidf(delta[i] + inv_sigmoid(ref[i], eps));
 }
 
+// Layer 0 of the Deformable-DETR variant (reference models/deformable_decoder.py:141-149 and memotr.py:148-158): the box
+// head refines all four coordinates of the 4-d reference, the decoder only xy and takes sigmoid(delta) for wh.  Both boxes
+// from one read of `delta`, one thread per row of four; element for element the arithmetic of refine_boxes_fwd_kernel
+// (`dec` wh: the same sigmoid with inverse_sigmoid(0.5) == 0 added).  VEC: all four pointers are 16-byte aligned.
+template <bool VEC>
+__global__ __launch_bounds__(256) void refine_boxes_split_fwd_kernel(const float *__restrict__ delta,
+                                                                    const float *__restrict__ ref, long n_rows,
+                                                                    float eps, float *__restrict__ head,
+                                                                    float *__restrict__ dec) {
+    for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (long)gridDim.x * blockDim.x) {
+        float4 d, f;
+        if (VEC) {
+            d = reinterpret_cast<const float4 *>(delta)[r];
+            f = reinterpret_cast<const float4 *>(ref)[r];
+        } else {
+            d = make_float4(delta[4 * r], delta[4 * r + 1], delta[4 * r + 2], delta[4 * r + 3]);
+            f = make_float4(ref[4 * r], ref[4 * r + 1], ref[4 * r + 2], ref[4 * r + 3]);
+        }
+        float4 h, c;
+        h.x = sigmoidf(d.x + inv_sigmoid(f.x, eps));
+        h.y = sigmoidf(d.y + inv_sigmoid(f.y, eps));
+        h.z = sigmoidf(d.z + inv_sigmoid(f.z, eps));
+        h.w = sigmoidf(d.w + inv_sigmoid(f.w, eps));
+        c.x = h.x;
+        c.y = h.y;
+        c.z = sigmoidf(d.z);
+        c.w = sigmoidf(d.w);
+        if (VEC) {
+            reinterpret_cast<float4 *>(head)[r] = h;
+            reinterpret_cast<float4 *>(dec)[r] = c;
+        } else {
+            head[4 * r] = h.x; head[4 * r + 1] = h.y; head[4 * r + 2] = h.z; head[4 * r + 3] = h.w;
+            dec[4 * r] = c.x; dec[4 * r + 1] = c.y; dec[4 * r + 2] = c.z; dec[4 * r + 3] = c.w;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void refine_boxes_bwd_kernel(const float *__restrict__ out,
                                                               const float *__restrict__ ref,
                                                               const float *__restrict__ g, long n, float eps,
@@ -1410,6 +1447,22 @@ int clipops_refine_boxes_fwd_f32(const float *delta, const float *ref, long n, f
     hipLaunchKernelGGL(refine_boxes_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, delta, ref, n,
                        eps, out);
     return check_launch("refine_boxes_fwd_kernel");
+}
+
+int clipops_refine_boxes_split_fwd_f32(const float *delta, const float *ref, long n_rows, float eps, float *out_head,
+                                       float *out_dec, void *stream) {
+    if (n_rows < 0) return fail(1, "clipops_refine_boxes_split_fwd_f32: negative count");
+    if (n_rows == 0) { g_err[0] = 0; return 0; }
+    if (!delta || !ref || !out_head || !out_dec) return fail(1, "clipops_refine_boxes_split_fwd_f32: null pointer");
+    if (out_head == out_dec) return fail(1, "clipops_refine_boxes_split_fwd_f32: the two outputs alias");
+    const bool vec = (((uintptr_t)delta | (uintptr_t)ref | (uintptr_t)out_head | (uintptr_t)out_dec) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(refine_boxes_split_fwd_kernel<true>, dim3(grid_for(n_rows)), dim3(256), 0,
+                           (hipStream_t)stream, delta, ref, n_rows, eps, out_head, out_dec);
+    else
+        hipLaunchKernelGGL(refine_boxes_split_fwd_kernel<false>, dim3(grid_for(n_rows)), dim3(256), 0,
+                           (hipStream_t)stream, delta, ref, n_rows, eps, out_head, out_dec);
+    return check_launch("refine_boxes_split_fwd_kernel");
 }
 
 int clipops_refine_boxes_bwd_f32(const float *out, const float *ref, const float *grad_out, long n, float eps,

@@ -352,6 +352,46 @@ def refine_boxes(delta: torch.Tensor, ref: torch.Tensor, eps: float = 1e-5) -> t
     return _RefineBoxes.apply(delta.contiguous(), ref.contiguous(), float(eps))
 
 
+class _RefineBoxesSplit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, delta, ref, eps):
+        head, dec = torch.empty_like(delta), torch.empty_like(delta)
+        L = _lib()
+        L.check(L.lib.clipops_refine_boxes_split_fwd_f32(delta.data_ptr(), ref.data_ptr(), delta.numel() // 4, eps,
+                                                         head.data_ptr(), dec.data_ptr(), _stream(delta)),
+                "clipops_refine_boxes_split_fwd_f32")
+        ctx.save_for_backward(head, ref)
+        ctx.eps = eps
+        ctx.mark_non_differentiable(dec)
+        return head, dec
+
+    @staticmethod
+    def backward(ctx, g, _g_dec):
+        return _RefineBoxes.backward(ctx, g)         # the refine backward on `head`: `dec` carries no gradient
+
+
+def refine_boxes_split_reference(delta: torch.Tensor, ref: torch.Tensor, eps: float = 1e-5):
+    """The host statement of ``refine_boxes_split``: the model's box head at level 0 (reference models/memotr.py:148-158)
+    and the decoder's own refinement from the 2-d slice of the reference (models/deformable_decoder.py:141-149)."""
+    from ..utils.utils import inverse_sigmoid_reference
+    head = (delta + inverse_sigmoid_reference(ref, eps)).sigmoid()
+    with torch.no_grad():
+        xy = delta[..., :2] + inverse_sigmoid_reference(ref[..., :2], eps)
+        dec = torch.cat((xy, delta[..., 2:]), -1).sigmoid()
+    return head, dec
+
+
+def refine_boxes_split(delta: torch.Tensor, ref: torch.Tensor, eps: float = 1e-5):
+    """Layer 0 of the Deformable-DETR variant, (..., 4) tensors of one shape -> (head, dec):
+    head = sigmoid(delta + inverse_sigmoid(ref)), differentiable; dec = (head xy, sigmoid(delta wh)), no gradient.
+    One kernel for CUDA fp32 tensors, the torch composition for everything else."""
+    if delta.shape != ref.shape or delta.shape[-1] != 4:
+        raise RuntimeError("refine_boxes_split: delta and ref must have the same (..., 4) shape")
+    if fused(delta, ref) and delta.dtype == torch.float32 and ref.dtype == torch.float32:
+        return _RefineBoxesSplit.apply(delta.contiguous(), ref.contiguous(), float(eps))
+    return refine_boxes_split_reference(delta, ref, eps)
+
+
 # --------------------------------------------------------------------------------------------------------------
 # bias gradients of the query-sized linears
 # --------------------------------------------------------------------------------------------------------------

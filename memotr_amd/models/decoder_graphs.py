@@ -7,7 +7,8 @@ rate.  A captured graph replays the whole per-layer chain 
 What is captured: ``DeformableDecoder.forward``'s loop as a tensor-in / tensor-out module (``DecoderLoop``): per layer anchors -> sine embedding -> ``ref_point_head`` (x ``query_scale``) -> the decoder layer
 (self-attention over the queries, MSDeformAttn cross-attention through the fused HIP kernels, FFN) -> box head ->
 refined reference (detached for the next layer).  ``torch.cuda.make_graphed_callables`` records its forward and its
-backward as two graphs.
+backward as two graphs.  The Deformable-DETR variant (``use_dab=False``) has a loop of its own, ``PlainDecoderLoop``: the
+query position is an input and layer 0 works on 2-d references.
 
 Constraints handled here:
   * static shapes: the query count (300 detect + n track queries) is padded to a multiple of ``BUCKET`` with masked
@@ -90,6 +91,65 @@ class DecoderLoop(nn.Module):
         return torch.stack(outs), torch.stack(refs), torch.stack(layer_inputs), torch.stack(boxes)
 
 
+class PlainDecoderLoop(nn.Module):
+    """``DecoderLoop`` for the Deformable-DETR variant (``use_dab=False`` with box refinement, the eager branch of
+    ``DeformableDecoder.forward``): the query position is an input, constant over the layers -- no anchor embedding, no
+    ``ref_point_head``, no ``query_scale`` (the decoder does not own them).  Layer 0 samples around the 2-d slice of the
+    4-d input reference and refines only xy; the model's box head refines all four at that level, so the one ``delta``
+    of layer 0 gives two boxes (``clip_ops.refine_boxes_split``): ``boxes[0]`` is the head's, with its graph, ``refs[0]``
+    the decoder's, detached.  From layer 1 on both are the same expression, as with DAB anchors.
+
+    Every module appears once in this tree (see ``DecoderLoop``): ``layers`` and ``bbox_embed``."""
+
+    def __init__(self, decoder, spatial_shapes, level_start_index):
+        super().__init__()
+        self.layers = nn.ModuleList(decoder.layers)
+        self.bbox_embed = nn.ModuleList(decoder.bbox_embed)
+        self.nd = decoder.n_det_queries
+        self.merge_from = decoder.merge_det_track_layer
+        self._shapes = spatial_shapes
+        self._lsi = level_start_index
+
+    def forward(self, output, reference_points, query_pos, src, valid_ratios, ratios4, query_mask, src_padding_mask):
+        outs, refs, layer_inputs, boxes = [], [], [], []
+        from ..modules.ms_deform_attn import project_values
+        values = project_values([layer.cross_attn for layer in self.layers], src, src_padding_mask)
+        anchors = reference_points              # what track queries keep until the layers merge them
+        for lid, layer in enumerate(self.layers):
+            layer_inputs.append(output)
+            if lid == 0:
+                ref_in = reference_points[:, :, None, :2] * valid_ratios[:, None]
+            else:
+                ref_in = reference_points[:, :, None] * ratios4
+            merge = lid >= self.merge_from
+            output = layer(output, query_pos, ref_in, src, self._shapes, self._lsi, query_mask, src_padding_mask, merge,
+                           None if values is None else values[lid])
+            delta = self.bbox_embed[lid](output)
+            if lid == 0:
+                box, new_ref = clip_ops.refine_boxes_split(delta, reference_points)
+            else:
+                box = new_ref = refine_boxes(delta, reference_points)
+            boxes.append(box)
+            if merge:
+                reference_points = new_ref.detach()
+            else:   # track queries did not go through the layer: keep their anchors
+                reference_points = torch.cat((new_ref[:, :self.nd].detach(), anchors[:, self.nd:]), dim=1)
+            outs.append(output)
+            refs.append(reference_points)
+        return torch.stack(outs), torch.stack(refs), torch.stack(layer_inputs), torch.stack(boxes)
+
+
+def uses_dab(decoder) -> bool:
+    """Which of the two loops ``decoder`` runs (DAB anchors unless the owner says otherwise); part of the cache keys."""
+    return bool(getattr(decoder, "use_dab", True))
+
+
+def loop_for(decoder, spatial_shapes, level_start_index) -> nn.Module:
+    """The capturable loop of ``decoder``; the arguments are those ``DeformableDecoder._forward_graphed`` assembles."""
+    cls = DecoderLoop if uses_dab(decoder) else PlainDecoderLoop
+    return cls(decoder, spatial_shapes, level_start_index)
+
+
 def enabled() -> bool:
     return os.environ.get("MEMOTR_DECODER_GRAPHS", "1") != "0"
 
@@ -110,7 +170,7 @@ class DecoderGraphs(GraphCache):
         # extra_track_attn: a frame without tracks still carries one masked (padded) track slot in the graphed path,
         # and attention over keys that are ALL masked is 0 * inf -- its rows are sliced away, but the NaN reaches the
         # parameter gradients through the norms; those models keep the eager loop
-        return (enabled() and not self.failed and output.is_cuda and d.use_dab and d.bbox_embed is not None
+        return (enabled() and not self.failed and output.is_cuda and d.bbox_embed is not None
                 and (not d.use_checkpoint or os.environ.get("MEMOTR_CHECKPOINT_DECODER", "0") != "1")
                 and torch.is_grad_enabled() and src.requires_grad
                 and not torch.is_autocast_enabled() and output.dtype == torch.float32
@@ -125,8 +185,9 @@ class DecoderGraphs(GraphCache):
 
     def run(self, frame_slot: int, args, shapes, lsi, clip_key=None):
         """The decoder loop of frame ``frame_slot`` through its graph (captured on first use); None if capture failed."""
+        # (a capture bakes the kernel choice in; `use_dab`: a decoder toggled between the two loops never replays the other's)
         key = (frame_slot, tuple(a.shape for a in args), tuple(bool(a.requires_grad) for a in args),
-               self._geometry(shapes), clip_ops.config_key())          # (a capture bakes the kernel choice in)
+               self._geometry(shapes), clip_ops.config_key(), uses_dab(self.decoder))
         entry = self.lookup(key, lambda: self._capture(args, shapes, lsi))
         if entry is None:
             return None
@@ -141,8 +202,8 @@ class DecoderGraphs(GraphCache):
         return tuple(map(tuple, host_shapes(shapes).tolist()))
 
     def _capture(self, args, shapes, lsi):
-        """Capture ``DecoderLoop`` as a function of (inputs..., flat parameters)."""
-        loop = DecoderLoop(self.decoder, shapes, lsi)
+        """Capture the decoder's loop as a function of (inputs..., flat parameters)."""
+        loop = loop_for(self.decoder, shapes, lsi)
         params = FlatParameters(loop, loop.named_parameters(), True, shared=self._flat)
 
         def run(*flat_in):           # (inputs..., flat parameters)

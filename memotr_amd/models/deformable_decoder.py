@@ -8,10 +8,10 @@ from torch.utils.checkpoint import checkpoint
 
 from ..modules import MSDeformAttn
 from ..modules.ms_deform_attn import project_values
-from ..functions.clip_ops import add_layer_norm
+from ..functions.clip_ops import add_layer_norm, refine_boxes_split
 from ..modules.attention import self_attention
 from ..modules.linear import row_linear
-from ..utils.utils import inverse_sigmoid, refine_boxes
+from ..utils.utils import refine_boxes
 from .decoder_graphs import DecoderGraphs
 from .mlp import MLP
 from .utils import get_activation_layer, get_clones, pos_to_pos_embed
@@ -56,8 +56,8 @@ class DeformableDecoder(nn.Module):
             g = self.__dict__["_infer_graphs"] = InferGraphs(None)
         return g
 
-    def _forward_graphed(self, tgt, reference_points, src, spatial_shapes, level_start_index, valid_ratios, query_mask,
-                         src_padding_mask, frame_slot, clip_key=None, infer=False):
+    def _forward_graphed(self, tgt, reference_points, src, spatial_shapes, level_start_index, valid_ratios, query_pos,
+                         query_mask, src_padding_mask, frame_slot, clip_key=None, infer=False):
         """The loop below with every iteration replayed from a hipGraph (models/decoder_graphs.py; ``infer``: the
         forward-only capture of models/infer_graphs.py).  Returns None when a capture fails; the caller then runs the
         eager loop."""
@@ -70,9 +70,15 @@ class DeformableDecoder(nn.Module):
             tgt = torch.cat((tgt, tgt.new_zeros(B, pad, C)), 1)
             reference_points = torch.cat((reference_points, reference_points.new_full((B, pad, 4), 0.5)), 1)
             query_mask = torch.cat((query_mask, query_mask.new_ones(B, pad)), 1)
+            if not self.use_dab:
+                query_pos = torch.cat((query_pos, query_pos.new_zeros(B, pad, C)), 1)
         ratios4 = torch.cat([valid_ratios, valid_ratios], -1)[:, None].contiguous()
         query_mask = query_mask.contiguous()
-        args = (tgt.contiguous(), reference_points.contiguous(), src, ratios4, query_mask, src_padding_mask)
+        if self.use_dab:       # (DecoderLoop)
+            args = (tgt.contiguous(), reference_points.contiguous(), src, ratios4, query_mask, src_padding_mask)
+        else:                  # (PlainDecoderLoop: the query position is an input, layer 0 samples around 2-d references)
+            args = (tgt.contiguous(), reference_points.contiguous(), query_pos.contiguous(), src,
+                    valid_ratios.contiguous(), ratios4, query_mask, src_padding_mask)
         if infer:
             res = self.infer_graphs().run_decode(self, args, spatial_shapes, level_start_index)
         else:
@@ -98,13 +104,15 @@ class DeformableDecoder(nn.Module):
         if (frame_slot is not None and reference_points.shape[-1] == 4 and src_padding_mask is not None
                 and self.graphs().usable(tgt, src)):
             res = self._forward_graphed(tgt, reference_points, src, src_spatial_shapes, src_level_start_index,
-                                        src_valid_ratios, query_mask, src_padding_mask, frame_slot, clip_key)
+                                        src_valid_ratios, query_pos, query_mask, src_padding_mask, frame_slot,
+                                        clip_key)
             if res is not None:
                 return res
         if (not torch.is_grad_enabled() and reference_points.shape[-1] == 4 and src_padding_mask is not None
                 and self.infer_graphs().decode_usable(self, tgt, src)):
             res = self._forward_graphed(tgt, reference_points, src, src_spatial_shapes, src_level_start_index,
-                                        src_valid_ratios, query_mask, src_padding_mask, None, infer=True)
+                                        src_valid_ratios, query_pos, query_mask, src_padding_mask, None,
+                                        infer=True)
             if res is not None:
                 return res
         nd = self.n_det_queries
@@ -140,11 +148,12 @@ class DeformableDecoder(nn.Module):
             if self.bbox_embed is not None:
                 delta = self.bbox_embed[lid](output)
                 if reference_points.shape[-1] == 4:
-                    new_ref = refine_boxes(delta, reference_points)
+                    box = new_ref = refine_boxes(delta, reference_points)
                 else:
-                    xy = delta[..., :2] + inverse_sigmoid(reference_points)
-                    new_ref = torch.cat((xy, delta[..., 2:]), -1).sigmoid()
-                boxes.append(new_ref)
+                    # 2-d references (layer 0 of the variant): the decoder refines xy only, the model's box head all
+                    # four coordinates of the 4-d reference -- both from this one delta (clip_ops.refine_boxes_split)
+                    box, new_ref = refine_boxes_split(delta, ref_backup)
+                boxes.append(box)
                 if not merge:   # track queries did not go through the layer: keep their anchors
                     keep = reference_points if self.use_dab else ref_backup
                     reference_points = torch.cat((new_ref[:, :nd].detach(), keep[:, nd:]), dim=1)
@@ -152,7 +161,8 @@ class DeformableDecoder(nn.Module):
                     reference_points = new_ref.detach()
             outs.append(output)
             refs.append(reference_points)
-        # ``boxes``: the refined boxes of every layer BEFORE the detach -- exactly what the box head computes from
+        # ``boxes``: the refined boxes of every layer BEFORE the detach (without DAB anchors, at layer 0: refined from
+        # the full 4-d reference) -- exactly what the box head computes from
         # the same layer output, reference and (aliased) bbox_embed weights (reference models/memotr.py:131-143
         # recomputes it: 3 GEMMs + inverse_sigmoid + sigmoid per layer, forward and backward).  The decoder's own
         # use of them is detached, so handing this one copy to the head leaves values and gradients unchanged.

@@ -19,7 +19,7 @@ import torch
 
 from ..functions import clip_ops
 from ..utils.nested_tensor import NestedTensor
-from .decoder_graphs import DecoderGraphs, DecoderLoop
+from .decoder_graphs import DecoderGraphs, loop_for, uses_dab
 from .graph_cache import GraphCache
 from .graph_capture import checked_capture, encode_key_parts, geometry_pins
 
@@ -164,16 +164,16 @@ class InferGraphs:
     # ------------------------------------------------------------------ decoder loop
     def decode_usable(self, decoder, output, src) -> bool:
         return (enabled() and not torch.is_grad_enabled() and not decoder.training and output.is_cuda
-                and decoder.use_dab and decoder.bbox_embed is not None and not torch.is_autocast_enabled()
+                and decoder.bbox_embed is not None and not torch.is_autocast_enabled()
                 and output.dtype == torch.float32 and src.dtype == torch.float32 and not self.decode.failed
                 and not any(getattr(layer, "extra_track_attn", False) for layer in decoder.layers))
 
     def run_decode(self, decoder, args, shapes, lsi):
         key = (tuple(a.shape for a in args), DecoderGraphs._geometry(shapes), clip_ops.config_key(),
-               _fingerprint(decoder))
+               _fingerprint(decoder), uses_dab(decoder))
 
         def make_fn():
-            loop = DecoderLoop(decoder, shapes, lsi).eval()
+            loop = loop_for(decoder, shapes, lsi).eval()
             return (lambda *xs: loop(*xs)), lambda: ({}, [shapes, lsi])
 
         out = self.decode.run(key, make_fn, args)

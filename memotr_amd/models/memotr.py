@@ -212,9 +212,10 @@ class MeMOTR(nn.Module):
         classes, boxes = [], []
         # with box refinement the decoder already evaluated this head (same layer output, same reference, aliased
         # bbox_embed weights) to move its anchors: reuse that one evaluation instead of repeating it per layer
-        # (DAB only: without DAB the decoder refines from the 2-d slice of the reference while this head adds the
-        # full 4-d inverse sigmoid at level 0, reference models/memotr.py:148-158 -- not the same boxes for tracks)
-        reuse = refined is not None and self.use_dab and self.transformer.decoder.bbox_embed is self.bbox_embed
+        # (without DAB the decoder refines from the 2-d slice of the reference at level 0 while this head adds the full
+        # 4-d inverse sigmoid, reference models/memotr.py:148-158 -- not the same boxes for tracks: `refined[0]` is then
+        # the head's box, which the decoder computes next to its own, clip_ops.refine_boxes_split)
+        reuse = refined is not None and self.transformer.decoder.bbox_embed is self.bbox_embed
         per_layer = outputs.unbind(0)          # one backward node for the six uses (a select each: zero-fill + copy)
         n_lvl, B_, Nq_, C_ = outputs.shape
         batched_heads = reuse and all(isinstance(m, nn.Linear) for m in self.class_embed)
