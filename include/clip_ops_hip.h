@@ -256,6 +256,75 @@ int clipops_result_rows_f32(const float *boxes, const float *scores, const int64
                             int K, int64_t frame, float ori_w, float ori_h, float score_thresh, float area_thresh,
                             float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream);
 
+/* ---- track hand-over between two frames of a training clip: one gather, one scatter ----
+ * The active track set of frame t + 1 is a row-by-row copy of the decoder's outputs of frame t and of the tracks carried
+ * into it (reference models/criterion.py:166-194 + :354-367, models/query_updater.py:160-200 without drop / insert
+ * augmentation): which output row comes from where is known to the host once the assignment is solved, so it uploads a
+ * table and these two launches replace the per-field gathers, concatenations, the row selection and their ~40 backward
+ * nodes.  (Added without a new CLIPOPS_ABI_VERSION, like clipops_refine_boxes_split_fwd_f32: no entry point changed.)
+ *
+ * Sources: row r of source i is src.ptr[i] + r * src.row_stride[i] (element strides; the columns of a row are dense --
+ * the decoder's outputs are views of padded graph buffers).  Widths: K logits, 4 box / reference columns, C embedding
+ * columns, QW = C (use_dab) or 2C query columns. */
+enum {
+    CLIPOPS_HO_LOGITS = 0,   /* (n_det + n_tracks, K)   model output: pred_logits */
+    CLIPOPS_HO_BOXES,        /* (n_det + n_tracks, 4)   pred_bboxes, cxcywh */
+    CLIPOPS_HO_OUTPUTS,      /* (n_det + n_tracks, C)   last decoder layer's output */
+    CLIPOPS_HO_QUERIES,      /* (n_det, C)              the queries entering the last decoder layer */
+    CLIPOPS_HO_LAST_REF,     /* (n_det, 4)              last_ref_pts */
+    CLIPOPS_HO_INIT_REF,     /* (n_det, 4)              init_ref_pts */
+    CLIPOPS_HO_DET_EMBED,    /* (n_det, >= C)           det_query_embed; read (and required) only when !use_dab */
+    CLIPOPS_HO_PREV_REF,     /* (n_tracks, 4)           the carried tracks' ref_pts */
+    CLIPOPS_HO_PREV_LONG,    /* (n_tracks, C)           long_memory */
+    CLIPOPS_HO_PREV_LAST,    /* (n_tracks, C)           last_output */
+    CLIPOPS_HO_PREV_QUERY,   /* (n_tracks, QW)          query_embed */
+    CLIPOPS_HO_PREV_IOU,     /* (n_tracks, 1)           iou */
+    CLIPOPS_HO_N_SOURCES
+};
+typedef struct {
+    const float *ptr[CLIPOPS_HO_N_SOURCES];
+    long row_stride[CLIPOPS_HO_N_SOURCES];
+} clipops_handover_sources;
+typedef struct {
+    float *ptr[CLIPOPS_HO_N_SOURCES];
+} clipops_handover_grads;
+
+/* Forward: base (n_keep, W) contiguous, W = K + 8 + 3C + QW + 1, columns
+ *   logits | boxes | ref_pts | output_embed | long_memory | last_output | query_embed | iou,
+ * and the int64 fields ids, matched_idx (n_keep each).  Output row o is described by table[3o .. 3o+2] = (kind, s, g):
+ *   kind 0, carried track s:  logits, boxes, output_embed = model row n_det + s;  ref_pts, long_memory, last_output,
+ *           query_embed = the previous set's row s;  m = prev_matched[s] (the ground truth it owns, -1: none);
+ *           iou = m >= 0 ? IoU(box, gt_boxes[m]) : previous iou;  ids = prev_ids[s];  matched_idx = m.
+ *   kind 1, new track from detect query s matched to ground truth g:  logits, boxes, output_embed = model row s;
+ *           ref_pts = last_ref[s];  last_output = outputs[s];  long_memory = queries[s];
+ *           query_embed = queries[s] (use_dab) or det_embed[s][:C] | queries[s];
+ *           iou = IoU(box, gt_boxes[g]);  ids = gt_ids[g];  matched_idx = g.
+ *   kind 2, unclaimed detection s:  as kind 1 with ref_pts = init_ref[s];  iou = 0;  ids = matched_idx = -1.
+ * Then ids = iou < 0.5 ? -1 : ids on every row.  The IoU is the arithmetic of clipops_pair_iou_f32 (one device function);
+ * everything else is a copy, bit for bit.  One workgroup per output row.  A table row that points outside its source
+ * (s, g or prev_matched[s] out of range, unknown kind) yields a row of zeros with ids = matched_idx = -1: nothing is read
+ * or written out of bounds.  prev_* may be NULL when n_tracks == 0.  n_keep == 0 launches nothing. */
+int clipops_handover_fwd_f32(const clipops_handover_sources *src, const int64_t *prev_ids, const int64_t *prev_matched,
+                             const float *gt_boxes, const int64_t *gt_ids, const int64_t *table, int n_keep, int n_det,
+                             int n_tracks, int n_gt, int K, int C, int use_dab, float *base, int64_t *ids,
+                             int64_t *matched_idx, void *stream);
+
+/* Backward: from grad_base (n_keep, W) contiguous, the WHOLE gradient tensor of every differentiable source, each
+ * contiguous, NULL = not wanted:
+ *   grad.ptr[OUTPUTS], [QUERIES] (n_q, C);  [LAST_REF], [INIT_REF] (n_q, 4);  [DET_EMBED] (n_det, det_cols), !use_dab;
+ *   [PREV_REF] (n_tracks, 4);  [PREV_LONG], [PREV_LAST] (n_tracks, C);  [PREV_QUERY] (n_tracks, QW).
+ * (logits, boxes and iou take no gradient: grad.ptr of these must be NULL.)
+ * n_q >= n_det + n_tracks is the row count of the model-output tensors (padded query slots behind the live ones).
+ * A source row feeds at most one output row, so the kernel walks the SOURCE rows -- one workgroup per model row r < n_q,
+ * then one per previous-set row -- through the inverse tables: inv_q[r] / inv_prev[j] = the output row that reads model
+ * row r / previous row j, or -1.  It writes the sum of the columns that came from that row (output_embed + last_output
+ * and query_embed + long_memory of a new or unclaimed row: two terms, order-free) and zeros everywhere else: no atomics,
+ * no zero-fill beforehand, the same bits every time.  An inverse entry outside [0, n_keep), or one whose table row does
+ * not point back at the source row, counts as -1. */
+int clipops_handover_bwd_f32(const float *grad_base, const int64_t *table, const int64_t *inv_q, const int64_t *inv_prev,
+                             int n_keep, int n_q, int n_det, int n_tracks, int K, int C, int use_dab, int det_cols,
+                             const clipops_handover_grads *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,7 +60,21 @@ SYMBOLS = {
     "clipops_refine_boxes_split_fwd_f32": ([c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p], c_int),
     "clipops_result_rows_f32": ([c_void_p] * 4 + [c_int, c_int, ctypes.c_int64] + [c_float] * 4 + [c_void_p] * 3 +
                                 [c_int, c_void_p], c_int),
+    "clipops_handover_fwd_f32": ([c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4, c_int),
+    "clipops_handover_bwd_f32": ([c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_void_p], c_int),
 }
+
+# clipops_handover_sources / clipops_handover_grads (include/clip_ops_hip.h); the index of a source is its position here
+HANDOVER_SOURCES = ("logits", "boxes", "outputs", "queries", "last_ref", "init_ref", "det_embed", "prev_ref",
+                    "prev_long", "prev_last", "prev_query", "prev_iou")
+
+
+class HandoverSources(ctypes.Structure):
+    _fields_ = [("ptr", c_void_p * len(HANDOVER_SOURCES)), ("row_stride", c_long * len(HANDOVER_SOURCES))]
+
+
+class HandoverGrads(ctypes.Structure):
+    _fields_ = [("ptr", c_void_p * len(HANDOVER_SOURCES))]
 
 
 lib, check = _cabi.bind("libclip_ops_hip.so", "clipops", SYMBOLS, ABI_VERSION)

@@ -254,6 +254,12 @@ def clip_forward_backward(model: nn.Module, criterion, batch: dict, device, use_
     if upd is not None:
         upd.__dict__["_keep_rows_ok"] = hint
 
+    # ... and with the rows known to the host, the whole active set of the next frame is one gather
+    # (models/criterion.py: finish_tracks with state["handover"], include/clip_ops_hip.h: clipops_handover_*), which the
+    # updater's select_active_tracks hands on as it is; frames it does not cover take the composed path.
+    # MEMOTR_FUSED_HANDOVER=0: always the composed path.
+    handover = (hint and torch.device(device).type == "cuda" and os.environ.get("MEMOTR_FUSED_HANDOVER", "1") != "0")
+
     def set_up():
         tr = TrackInstances.init_tracks(batch=batch, hidden_dim=core.hidden_dim, num_classes=core.num_classes,
                                         device=device, use_dab=use_dab)
@@ -291,6 +297,7 @@ def clip_forward_backward(model: nn.Module, criterion, batch: dict, device, use_
                 on_side.difference_update(range(frame_idx, clip_len))
             res = model(tracks=tracks, encoded=encoded.pop(frame_idx))
             pending = criterion.begin_frame(model_outputs=res, tracked_instances=tracks, frame_idx=frame_idx)
+            pending["handover"], pending["gather"] = handover, frame_idx < clip_len - 1
             if not lazy and frame_idx in starts and starts.index(frame_idx) + 1 < len(chunks):
                 encode_chunk(starts.index(frame_idx) + 1)     # queued before the host blocks on this frame's costs
             if DEFER_LOSSES:

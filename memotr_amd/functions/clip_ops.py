@@ -7,6 +7,7 @@ compare the kernels with.  ``fused(t)`` decides: CUDA fp32 tensors use the kerne
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -219,6 +220,177 @@ def pair_iou_reference(boxes, tgt_boxes, gidx=None):
     from ..utils.box_ops import box_cxcywh_to_xyxy
     tb = tgt_boxes if gidx is None else tgt_boxes[gidx]
     return paired_iou(box_cxcywh_to_xyxy(boxes), box_cxcywh_to_xyxy(tb))
+
+
+# --------------------------------------------------------------------------------------------------------------
+# track hand-over between two frames (include/clip_ops_hip.h: clipops_handover_*)
+# --------------------------------------------------------------------------------------------------------------
+HANDOVER_CARRIED, HANDOVER_NEW, HANDOVER_UNCLAIMED = 0, 1, 2
+# the differentiable sources, in the order ``handover`` takes them (det_embed: None under DAB)
+HANDOVER_DIFF = ("outputs", "queries", "last_ref", "init_ref", "det_embed", "prev_ref", "prev_long", "prev_last",
+                 "prev_query")
+
+
+def handover_tables(n_det: int, n_q: int, n_tracks: int, new_q, new_g, free_q, keep):
+    """Host side of the hand-over (numpy in, one int64 numpy vector out): the row table of the active set and its
+    inverse.  Rows of (carried tracks; new tracks; unclaimed detections) are numbered as the composed path concatenates
+    them; ``keep`` picks the active ones, in order.  Returns ``[table (n_keep, 3) | inv_q (n_q) | inv_prev (n_tracks)]``
+    flattened: table row o = (kind, source row, ground truth); inv_q[r] / inv_prev[j] = the output row that reads model
+    row r / previous-set row j, or -1."""
+    import numpy as np
+    n_new, n_free = len(new_q), len(free_q)
+    kind = np.concatenate((np.full((n_tracks,), HANDOVER_CARRIED, dtype=np.int64),
+                           np.full((n_new,), HANDOVER_NEW, dtype=np.int64),
+                           np.full((n_free,), HANDOVER_UNCLAIMED, dtype=np.int64)))
+    src = np.concatenate((np.arange(n_tracks, dtype=np.int64), np.asarray(new_q, dtype=np.int64),
+                          np.asarray(free_q, dtype=np.int64)))
+    gt = np.concatenate((np.full((n_tracks,), -1, dtype=np.int64), np.asarray(new_g, dtype=np.int64),
+                         np.full((n_free,), -1, dtype=np.int64)))
+    keep = np.asarray(keep, dtype=np.int64)
+    table = np.stack((kind[keep], src[keep], gt[keep]), axis=1)
+    rows = np.arange(len(keep), dtype=np.int64)
+    carried = table[:, 0] == HANDOVER_CARRIED
+    inv_q = np.full((n_q,), -1, dtype=np.int64)
+    inv_q[np.where(carried, n_det + table[:, 1], table[:, 1])] = rows
+    inv_prev = np.full((n_tracks,), -1, dtype=np.int64)
+    inv_prev[table[carried, 1]] = rows[carried]
+    return np.concatenate((table.reshape(-1), inv_q, inv_prev))
+
+
+def _handover_views(tables, n_keep, n_q, n_tracks):
+    table = tables[:3 * n_keep]
+    inv_q = tables[3 * n_keep:3 * n_keep + n_q]
+    inv_prev = tables[3 * n_keep + n_q:3 * n_keep + n_q + n_tracks]
+    return table, inv_q, inv_prev
+
+
+def _rows_dense(t):
+    """A 2-d view the kernels can address as base + row * stride (dense columns), else a contiguous copy."""
+    return t if t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= 0 else t.contiguous()
+
+
+class _Handover(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, outputs, queries, last_ref, init_ref, det_embed, prev_ref, prev_long, prev_last, prev_query,
+                logits, boxes, prev_iou, prev_ids, prev_matched, gt_boxes, gt_ids, tables, n_keep, n_det):
+        L = _lib()
+        use_dab = det_embed is None
+        n_q, C, K = outputs.shape[0], outputs.shape[1], logits.shape[1]
+        n_tracks, n_gt = prev_ref.shape[0], gt_boxes.shape[0]
+        QW = C if use_dab else 2 * C
+        named = dict(logits=logits, boxes=boxes, outputs=outputs, queries=queries, last_ref=last_ref, init_ref=init_ref,
+                     det_embed=det_embed, prev_ref=prev_ref, prev_long=prev_long, prev_last=prev_last,
+                     prev_query=prev_query, prev_iou=prev_iou.reshape(-1, 1))
+        widths = dict(logits=K, boxes=4, outputs=C, queries=C, last_ref=4, init_ref=4, det_embed=C, prev_ref=4,
+                      prev_long=C, prev_last=C, prev_query=QW, prev_iou=1)
+        src, keep = L.HandoverSources(), []
+        for i, name in enumerate(L.HANDOVER_SOURCES):
+            t = named[name]
+            if t is None or t.shape[0] == 0:
+                continue
+            lead = n_tracks if name.startswith("prev_") else (n_det if name == "det_embed" else n_det + n_tracks)
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < lead or (
+                    t.shape[1] != widths[name] and not (name == "det_embed" and t.shape[1] >= C)):
+                raise RuntimeError(f"handover: source {name} has shape {tuple(t.shape)} ({t.dtype})")
+            t = _rows_dense(t.detach())
+            keep.append(t)
+            src.ptr[i], src.row_stride[i] = t.data_ptr(), t.stride(0)
+        if n_q != queries.shape[0] or n_q != last_ref.shape[0] or n_q != init_ref.shape[0]:
+            raise RuntimeError("handover: the model-output sources differ in their row counts")
+        if tables.dtype != torch.int64 or tables.numel() != 3 * n_keep + n_q + n_tracks:
+            raise RuntimeError("handover: the table does not have 3 * n_keep + n_q + n_tracks int64 entries")
+        tables = tables.contiguous()
+        prev_ids, prev_matched, gt_boxes, gt_ids = (t.contiguous() for t in (prev_ids, prev_matched, gt_boxes, gt_ids))
+        if n_tracks and (prev_ids.shape[0] != n_tracks or prev_matched.shape[0] != n_tracks):
+            raise RuntimeError("handover: ids / matched_idx of the previous set do not have one entry per track")
+        dev = outputs.device
+        base = torch.empty((n_keep, K + 8 + 3 * C + QW + 1), dtype=torch.float32, device=dev)
+        ints = torch.empty((2, n_keep), dtype=torch.int64, device=dev)
+        L.check(L.lib.clipops_handover_fwd_f32(
+            ctypes.byref(src), prev_ids.data_ptr() if n_tracks else None, prev_matched.data_ptr() if n_tracks else None,
+            gt_boxes.data_ptr(), gt_ids.data_ptr(), tables.data_ptr(), n_keep, n_det, n_tracks, n_gt, K, C,
+            int(use_dab), base.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), _stream(outputs)),
+            "clipops_handover_fwd_f32")
+        ctx.save_for_backward(tables)
+        ctx.dims = (n_keep, n_q, n_det, n_tracks, K, C, use_dab, 0 if det_embed is None else det_embed.shape[1], QW)
+        ctx.mark_non_differentiable(ints)
+        return base, ints
+
+    @staticmethod
+    def backward(ctx, g_base, _g_ints):
+        L = _lib()
+        (tables,) = ctx.saved_tensors
+        n_keep, n_q, n_det, n_tracks, K, C, use_dab, det_cols, QW = ctx.dims
+        table, inv_q, inv_prev = _handover_views(tables, n_keep, n_q, n_tracks)
+        g_base = g_base.contiguous()
+        shapes = dict(outputs=(n_q, C), queries=(n_q, C), last_ref=(n_q, 4), init_ref=(n_q, 4),
+                      det_embed=(n_det, det_cols), prev_ref=(n_tracks, 4), prev_long=(n_tracks, C),
+                      prev_last=(n_tracks, C), prev_query=(n_tracks, QW))
+        wanted = [name for i, name in enumerate(HANDOVER_DIFF) if ctx.needs_input_grad[i]]
+        # every gradient is a slice of ONE allocation, written in full by the one launch (no zero-fill)
+        flat = torch.empty((sum(shapes[n][0] * shapes[n][1] for n in wanted),), dtype=torch.float32, device=g_base.device)
+        grads, out, pos = L.HandoverGrads(), {}, 0
+        for name in wanted:
+            r, c = shapes[name]
+            out[name] = flat[pos:pos + r * c].view(r, c)
+            pos += r * c
+            if r * c:
+                grads.ptr[L.HANDOVER_SOURCES.index(name)] = out[name].data_ptr()
+        if flat.numel():
+            L.check(L.lib.clipops_handover_bwd_f32(
+                g_base.data_ptr(), table.data_ptr(), inv_q.data_ptr(), inv_prev.data_ptr() if n_tracks else None,
+                n_keep, n_q, n_det, n_tracks, K, C, int(use_dab), det_cols, ctypes.byref(grads), _stream(g_base)),
+                "clipops_handover_bwd_f32")
+        return tuple(out.get(name) for name in HANDOVER_DIFF) + (None,) * 10
+
+
+def handover(outputs, queries, last_ref, init_ref, det_embed, prev_ref, prev_long, prev_last, prev_query, logits, boxes,
+             prev_iou, prev_ids, prev_matched, gt_boxes, gt_ids, tables, n_keep: int, n_det: int):
+    """The active track set of the next frame as ONE gather (and one scatter backward): -> (base (n_keep, W) with the
+    columns of ``TrackInstances.PACKED_FLOAT``, ids (n_keep,), matched_idx (n_keep,)).  The nine leading arguments are
+    the differentiable sources (``HANDOVER_DIFF``; ``det_embed`` None: DAB queries of width C); ``logits``, ``boxes``
+    and ``prev_iou`` are copied without a gradient (the composed path's gradient for them is exactly zero: the query
+    updater reads the logits through a comparison and the boxes detached).  All 2-d with dense columns, any row stride;
+    ``tables`` from ``handover_tables``, on the device.  See include/clip_ops_hip.h for the row kinds."""
+    base, ints = _Handover.apply(outputs, queries, last_ref, init_ref, det_embed, prev_ref, prev_long, prev_last,
+                                 prev_query, logits, boxes, prev_iou, prev_ids, prev_matched, gt_boxes, gt_ids, tables,
+                                 n_keep, n_det)
+    return base, ints[0], ints[1]
+
+
+def handover_reference(outputs, queries, last_ref, init_ref, det_embed, prev_ref, prev_long, prev_last, prev_query,
+                       logits, boxes, prev_iou, prev_ids, prev_matched, gt_boxes, gt_ids, tables, n_keep: int,
+                       n_det: int):
+    """``handover`` as torch gathers and selects (differentiable through autograd; what CPU tensors run)."""
+    n_q, C = outputs.shape
+    n_tracks = prev_ref.shape[0]
+    table, _, _ = _handover_views(tables, n_keep, n_q, n_tracks)
+    kind, s, g = table.view(n_keep, 3).unbind(1)
+    carried, new = (kind == HANDOVER_CARRIED), (kind == HANDOVER_NEW)
+    m = torch.where(carried, n_det + s, s)                     # row of the model's outputs
+    q = torch.where(carried, torch.zeros_like(s), s)           # detect query (any valid row where it is not read)
+
+    def prev(t):
+        width = 1 if t.dim() == 1 else t.shape[1]
+        if n_tracks == 0:
+            return t.new_zeros((n_keep, width))
+        return t.reshape(n_tracks, width)[torch.where(carried, s, torch.zeros_like(s))]
+
+    col = carried[:, None]
+    det_q = queries[q] if det_embed is None else torch.cat((det_embed[q][:, :C], queries[q]), dim=-1)
+    box = boxes[m]
+    ref = torch.where(col, prev(prev_ref), torch.where(new[:, None], last_ref[q], init_ref[q]))
+    g_own = torch.where(carried, prev(prev_matched).reshape(-1), g)
+    iou_gt = pair_iou_reference(box.detach(), gt_boxes, g_own.clamp(min=0))
+    iou = torch.where(carried, torch.where(g_own >= 0, iou_gt, prev(prev_iou).reshape(-1)),
+                      torch.where(new, iou_gt, torch.zeros_like(iou_gt)))
+    ids = torch.where(carried, prev(prev_ids).reshape(-1), torch.where(new, gt_ids[g.clamp(min=0)], torch.full_like(g, -1)))
+    base = torch.cat((logits[m].detach(), box.detach(), ref, outputs[m], torch.where(col, prev(prev_long), queries[q]),
+                      torch.where(col, prev(prev_last), outputs[q]), torch.where(col, prev(prev_query), det_q),
+                      iou[:, None]), dim=1)
+    ids = torch.where(iou < 0.5, torch.full_like(ids, -1), ids)
+    matched = torch.where(carried, g_own, torch.where(new, g, torch.full_like(g, -1)))
+    return base, ids, matched
 
 
 # --------------------------------------------------------------------------------------------------------------

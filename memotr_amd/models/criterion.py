@@ -21,7 +21,7 @@ import torch.distributed
 import torch.nn.functional as F
 
 from ..functions import clip_ops
-from ..structures.track_instances import TrackInstances
+from ..structures.track_instances import TrackInstances, _empty
 from ..utils.box_ops import box_cxcywh_to_xyxy, box_iou_union, generalized_box_iou
 from ..utils.utils import distributed_world_size, is_distributed
 from .matcher import HungarianMatcher
@@ -42,6 +42,11 @@ def rows_of(x: torch.Tensor, b: int, idx: torch.Tensor) -> torch.Tensor:
     """x[b][idx] for a 1-d index: index_select, whose backward is one index_add (advanced indexing differentiates
     through a sort-based accumulate, ~7 kernels for a handful of rows)."""
     return batch_item(x, b).index_select(0, idx)
+
+
+def _no_columns(n: int, device) -> torch.Tensor:
+    """An (n, 0) tensor: rows to count, nothing to store (shared: it has no element to modify)."""
+    return _empty((n, 0), device=device)
 
 
 def upload(values, dtype, device):
@@ -332,7 +337,17 @@ class ClipCriterion:
     @_fp32_island
     def finish_tracks(self, state: dict):
         """The assignment problems on the host, the index upload, and the track sets the next frame needs: returns
-        (tracked, new, unmatched).  Leaves in ``state`` what ``finish_losses`` reads."""
+        (tracked, new, unmatched).  Leaves in ``state`` what ``finish_losses`` reads.
+
+        ``state["handover"]`` (set by the training loop, where the query updater selects by ``keep_rows``): the host
+        also knows where every row of the next frame's ACTIVE set comes from, so that set is gathered by one kernel
+        (clip_ops.handover) instead of being composed from new / unmatched sets, concatenations and a row selection.
+        ``new`` and ``unmatched`` then only count their rows (their fields have no columns: nothing is gathered for
+        them) and ``unmatched._keep_rows`` carries the gathered set itself instead of the row index:
+        ``QueryUpdater.select_active_tracks`` hands it on as it is.  With ``state["gather"]`` False (the last frame of
+        a clip, whose tracks nobody reads) nothing is gathered at all.  A frame the kernel does not cover -- no ground
+        truth, an empty active set (the updater's fake track), tensors the kernels do not take,
+        MEMOTR_FUSED_HANDOVER=0 -- returns the three sets as without the switch."""
         model_outputs, tracked_instances, frame_idx = state["model_outputs"], state["tracked_instances"], state["frame_idx"]
         early, logits_all, boxes_all, n_gt_list = state["early"], state["logits_all"], state["boxes_all"], state["n_gt_list"]
         nd, dev, B, n_layers = self.n_det_queries, self.device, len(tracked_instances), len(state["layers"])
@@ -371,6 +386,11 @@ class ClipCriterion:
         new_tracks, unmatched = [], []
         n_det_out = len(model_outputs["det_query_embed"])
         per_clip = []                                   # what finish_losses reads, per clip of the batch
+        if state.get("handover", False):
+            counted = self._handover(state, main_q, flags_h, (rows_layer, rows_q, rows_g), state.get("gather", True))
+            if counted is not None:
+                self.n_gts.append(sum(n_gt_list))
+                return (tracked_instances,) + counted
         for b in range(B):
             tr, gt = tracked_instances[b], gts[b]
             n_tr = len(tr)
@@ -449,6 +469,80 @@ class ClipCriterion:
         self.n_gts.append(sum(n_gt_list))
         state["per_clip"] = per_clip
         return tracked_instances, new_tracks, unmatched
+
+    def _handover(self, state: dict, main_q, flags_h, rows, gather: bool):
+        """The fused branch of ``finish_tracks``: per clip ONE upload (the matched triples of every layer for the losses,
+        the hand-over's row table and its inverse) and one launch that writes the active set.  Returns the list of
+        (new, unmatched) lists described in ``finish_tracks``, or None when a clip of the batch is not covered --
+        nothing has been queued then."""
+        model_outputs, tracked, gts = state["model_outputs"], state["tracked_instances"], \
+            self.gt_trackinstances_list[state["frame_idx"]]
+        nd, dev = self.n_det_queries, self.device
+        if os.environ.get("MEMOTR_FUSED_HANDOVER", "1") == "0" or not self.aux_loss:
+            return None
+        n_det_out = len(model_outputs["det_query_embed"])
+        outputs_all = model_outputs["outputs"]
+        plans = []
+        for b, (tr, gt) in enumerate(zip(tracked, gts)):
+            n_tr = len(tr)
+            fl = flags_h[b]
+            mq, mg = (np.asarray(x, dtype=np.int64) for x in main_q[b])
+            if fl is None or len(gt) == 0 or n_det_out != nd:
+                return None
+            unclaimed = np.ones((nd,), dtype=bool)
+            unclaimed[mq] = False
+            free_np = np.flatnonzero(unclaimed)
+            sc, idf, gtf = fl[:nd + n_tr], fl[nd + n_tr:nd + 2 * n_tr], fl[nd + 2 * n_tr:]
+            keep_np = np.concatenate((np.flatnonzero(sc[nd:nd + n_tr] | idf), n_tr + np.flatnonzero(sc[mq] | gtf[mg]),
+                                      n_tr + len(mq) + np.flatnonzero(sc[free_np])))
+            tensors = (batch_item(outputs_all, b), batch_item(model_outputs["pred_bboxes"], b), gt.boxes)
+            if (len(keep_np) == 0 or tr.ids.dtype != torch.int64 or gt.ids.dtype != torch.int64
+                    or any(t.dtype != torch.float32 for t in tensors)
+                    or (outputs_all.is_cuda and not clip_ops.fused(*tensors))):
+                return None
+            plans.append((n_tr, mq, mg, free_np, keep_np))
+        gather_fn = clip_ops.handover if outputs_all.is_cuda else clip_ops.handover_reference
+        C = outputs_all.shape[-1]
+        K = model_outputs["pred_logits"].shape[-1]
+        widths = [K, 4, 4, C, C, C, C if self.use_dab else 2 * C, 1]
+        new_tracks, unmatched, per_clip = [], [], []
+
+        def counted(n, tr):
+            """n rows, no columns: the set is never materialised, its length is all the query updater's entry sees"""
+            t = TrackInstances(frame_height=tr.frame_height, frame_width=tr.frame_width, device=dev)
+            t.ref_pts = t.query_embed = _no_columns(n, dev)
+            return t
+
+        for b, (n_tr, mq, mg, free_np, keep_np) in enumerate(plans):
+            tr, gt = tracked[b], gts[b]
+            lay_np, q_np, g_np = (np.concatenate([np.asarray(r, dtype=np.int64) for r in rr[b]]) for rr in rows)
+            n_pairs = len(q_np)
+            outputs = batch_item(outputs_all, b)
+            parts = (lay_np, q_np, g_np)
+            if gather:
+                parts += (clip_ops.handover_tables(nd, outputs.shape[0], n_tr, mq, mg, free_np, keep_np),)
+            up = upload(np.concatenate(parts), torch.long, dev)
+            per_clip.append({"idx": (up[:n_pairs], up[n_pairs:2 * n_pairs], up[2 * n_pairs:3 * n_pairs]), "n_tr": n_tr,
+                             "matched_idx": tr.matched_idx if n_tr > 0 else None})
+            new_tracks.append(counted(len(mq), tr))
+            unmatched.append(counted(len(free_np), tr))
+            if not gather:
+                continue
+            base, ids, matched = gather_fn(
+                outputs, batch_item(model_outputs["aux_outputs"][-1]["queries"], b),
+                batch_item(model_outputs["last_ref_pts"], b), batch_item(model_outputs["init_ref_pts"], b),
+                None if self.use_dab else model_outputs["det_query_embed"],
+                tr.ref_pts, tr.long_memory, tr.last_output, tr.query_embed,
+                batch_item(model_outputs["pred_logits"], b), batch_item(model_outputs["pred_bboxes"], b),
+                tr.iou, tr.ids, tr.matched_idx, gt.boxes, gt.ids, up[3 * n_pairs:], len(keep_np), nd)
+            # (meta as the composed path leaves it: cat_packed and [rows] rebuild the container with default sizes)
+            act = TrackInstances(frame_height=tr.frame_height, frame_width=tr.frame_width, device=dev)
+            act._set_packed(base, TrackInstances.PACKED_FLOAT, widths)
+            act.ids, act.matched_idx = ids, matched
+            # (QueryUpdater.select_active_tracks: the kept rows themselves -- valid for THIS threshold only)
+            unmatched[-1]._keep_rows = (act, float(self.keep_threshold))
+        state["per_clip"] = per_clip
+        return new_tracks, unmatched
 
     @_fp32_island
     def finish_losses(self, state: dict):

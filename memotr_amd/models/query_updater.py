@@ -172,6 +172,18 @@ class QueryUpdater(nn.Module):
             return [active[active.ids >= 0]]
         tracks = []
         for b in range(len(new_tracks)):
+            handed = unmatched_dets[b].__dict__.get("_keep_rows", None)
+            if handed is not None and isinstance(handed[0], TrackInstances):
+                # the criterion gathered the active set itself (models/criterion.py: finish_tracks with
+                # state["handover"], one kernel): new / unmatched only count their rows, there is nothing to
+                # concatenate or select
+                del unmatched_dets[b].__dict__["_keep_rows"]
+                if not (self.tp_drop_ratio == 0.0 and self.fp_insert_ratio == 0.0
+                        and self.__dict__.get("_keep_rows_ok", False) and handed[1] == float(self.update_threshold)):
+                    raise RuntimeError("the criterion handed over an active track set gathered for another "
+                                       "selection rule (threshold or augmentation changed within a clip)")
+                tracks.append(handed[0])
+                continue
             self._seed_memories(new_tracks[b])
             self._seed_memories(unmatched_dets[b])
             if self.tp_drop_ratio == 0.0 and self.fp_insert_ratio == 0.0:
