@@ -65,6 +65,11 @@ __global__ __launch_bounds__(256) void msda_fused_finish_kernel(const int64_t *_
 __global__ __launch_bounds__(256) void msda_fused_finish16_kernel(const int64_t *__restrict__ shapes, const PointSrc fs,
                                                                  long n_rows, int M, int L, int P,
                                                                  float *__restrict__ grad_proj, int offsets_done) {
+    // No contraction: the first butterfly step `dot += shfl(dot)` would otherwise become fma(a, g, neighbour's rounded
+    // product) -- the compiler fuses a product with several uses -- so the two lanes of a pair, and then all sixteen,
+    // would each subtract a dot of their own, and the one-lane-per-row form below could not have these bits
+    // (tests/test_msda_fused_truth_gpu.py: bwd_side_rows 1 against 0).
+#pragma clang fp contract(off)
     const int LP = L * P;
     const int t = threadIdx.x & 15;
     const long rows_pad = (n_rows + 3) & ~3L;
@@ -132,9 +137,11 @@ __global__ __launch_bounds__(256) void msda_fused_attn16_rows_kernel(const Point
 
 __global__ __launch_bounds__(256) void msda_fused_finish16_rows_kernel(const PointSrc fs, unsigned n_rows, unsigned M,
                                                                       float *__restrict__ grad_proj) {
+    // (every product a_t g_t rounded before it is added, as in msda_fused_finish16_kernel: no contraction here either)
+#pragma clang fp contract(off)
     for (unsigned pm = blockIdx.x * blockDim.x + threadIdx.x; pm < n_rows; pm += gridDim.x * blockDim.x) {
         const unsigned qrow = pm / M, m = pm - qrow * M;
-        f32x4 *gp = reinterpret_cast<f32x4 *>(grad_proj + ((size_t)qrow * (unsigned)fs.proj_stride + (unsigned)fs.n_off + m * 16u));
+        f32x4 *gp =reinterpret_cast<f32x4 *>(grad_proj + ((size_t)qrow * (unsigned)fs.proj_stride + (unsigned)fs.n_off + m * 16u));
         const f32x4 *ap = reinterpret_cast<const f32x4 *>(fs.attn + (size_t)pm * 16u);
         float a[16], g[16], d[16];
 #pragma unroll

@@ -20,9 +20,9 @@ Kernels asserted by name, bf16 and fp32:
               msda_bwd_d32_tile_lv<2[,bf16]> at margins 0 and 4, msda_bwd_generic (D = 16, 64)
 Not reached at these sizes (the shapes are not enlarged for them): msda_bwd_d32_tile_bins<3,...> -- it needs the
 two-items-per-thread LDS plan to fail, i.e. rows * P > 512, and a region has at most 85 rows; the split / soft / fused
-backward instantiations belong to the fused entry, whose Jacobians are out of scope here (their parity:
-tests/test_msda_fused_gpu.py).  The fused FORWARD is covered: truth is fed the points the kernel itself exposes
-(``fused_points``), so the in-kernel softmax is not part of the budget.
+backward instantiations belong to the fused entry: tests/test_msda_fused_truth_gpu.py holds them, the in-kernel softmax
+and the prologue's Jacobians to float64 truth (tests/msda_fused_truth.py).  The fused FORWARD here is fed the points the
+kernel itself exposes (``fused_points``), so the in-kernel softmax is not part of THIS file's budget.
 """
 import numpy as np
 import pytest
@@ -32,7 +32,8 @@ import msda_truth as mt
 
 pytestmark = pytest.mark.gpu
 
-OPTIONS = ("fwd_variant", "bwd_variant", "sel_level", "bwd_sorted", "fwd_win_bf16", "bwd_tile_margin", "bwd_bins_margin")
+OPTIONS = ("fwd_variant", "bwd_variant", "sel_level", "bwd_sorted", "fwd_win_bf16", "bwd_tile_margin", "bwd_bins_margin",
+           "bwd_split", "bwd_soft", "bwd_side_rows", "bwd_rows_block")
 
 
 @pytest.fixture(scope="module")
@@ -173,8 +174,8 @@ def test_backward_path_within_the_derived_bound(msda, hip_lib, path, case_id, bf
                          ids=["win", "gather"])
 def test_fused_forward_within_the_derived_bound_on_its_exposed_points(msda, hip_lib, variant, names, bf16):
     """The fused entry computes softmax and locations in-kernel; ``fused_points`` exposes the very bits it forms
-    (tests/test_msda_fwd_win_gpu.py pins that), so truth on those points budgets only the sampling and the sum.  The fused
-    backward's Jacobians are out of scope here."""
+    (tests/test_msda_fwd_win_gpu.py pins that), so truth on those points budgets only the sampling and the sum.  The softmax
+    itself and the fused backward's Jacobians: tests/test_msda_fused_truth_gpu.py."""
     from fused_helpers import make_case
     from memotr_amd.MultiScaleDeformableAttention import tag_host_shapes
     shapes = mt.GEOMETRIES["pyr4"][0]
