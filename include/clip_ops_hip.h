@@ -325,6 +325,70 @@ int clipops_handover_bwd_f32(const float *grad_base, const int64_t *table, const
                              int n_keep, int n_q, int n_det, int n_tracks, int K, int C, int use_dab, int det_cols,
                              const clipops_handover_grads *grad, void *stream);
 
+/* ---- track bank: the online tracker's bookkeeping for B sequences on fixed-size device tables ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the hand-over entries: no entry point changed.)
+ * The tracks of stream b live in `cap` slots; a track keeps its slot for life, ids[b][s] = -1 marks a free slot and a
+ * free slot holds zeros in every field.  All bank tensors are contiguous: ids, labels, disappear_time int64 (B, cap);
+ * boxes, ref_pts (B, cap, 4); logits, scores (B, cap, K); output_embed, long_memory, last_output (B, cap, C);
+ * query_embed (B, cap, QW), QW = C (use_dab) or 2C; next_id int64 (B,); counters int32 (B, 2) = live tracks after the
+ * last update, births that found no free slot (accumulated); free_list int32 (B, cap): workspace of the update. */
+typedef struct {
+    int64_t *ids, *labels, *disappear_time;
+    float *boxes, *ref_pts, *logits, *scores, *output_embed, *long_memory, *last_output, *query_embed;
+    int64_t *next_id;
+    int32_t *counters;
+    int32_t *free_list;
+} clipops_bank;
+
+/* The decoder's outputs for the B streams, each (B, n_det + cap, width) with a dense last axis: element (b, r, c) of
+ * source i is ptr[i][b * batch_stride[i] + r * row_stride[i] + c].  det_embed (n_det, >= C) with its row stride is read
+ * (and required) only when !use_dab. */
+enum {
+    CLIPOPS_BK_LOGITS = 0,   /* K   pred_logits */
+    CLIPOPS_BK_BOXES,        /* 4   pred_bboxes, cxcywh */
+    CLIPOPS_BK_OUTPUTS,      /* C   last decoder layer's output */
+    CLIPOPS_BK_LAST_REF,     /* 4   last_ref_pts */
+    CLIPOPS_BK_QUERIES,      /* C   the queries entering the last decoder layer */
+    CLIPOPS_BK_N_MODEL
+};
+typedef struct {
+    const float *ptr[CLIPOPS_BK_N_MODEL];
+    long batch_stride[CLIPOPS_BK_N_MODEL];
+    long row_stride[CLIPOPS_BK_N_MODEL];
+    const float *det_embed;
+    long det_row_stride;
+} clipops_bank_model;
+
+/* One frame of track management for every stream (reference models/runtime_tracker.py:36-101 and the inference branch
+ * of models/query_updater.py:160-166), one workgroup per stream, sigmoid(x) = 1 / (1 + expf(-x)) in float32:
+ *   live slot s (ids >= 0), from model row n_det + s:  boxes, logits, output_embed = the row;  scores = sigmoid(logits);
+ *     own = scores[labels];  disappear_time = own < track_score_thresh ? disappear_time + 1 : 0 (a NaN does not age);
+ *     disappear_time >= miss_tolerance: the slot is freed -- ids = -1 and every field of the row zero.
+ *   detect row r < n_det is born when max_k sigmoid(logits[r,k]) >= det_score_thresh and no score of the row is NaN; its
+ *     label is the lowest index of the maximum.  The j-th born row in row order takes the j-th slot in slot order that
+ *     was free WHEN THE CALL BEGAN (a slot freed by this call is reused from the next call on):  ids = next_id + j;
+ *     logits, boxes, output_embed = the row;  scores = sigmoid(logits);  ref_pts = last_ref row;  disappear_time = 0;
+ *     last_output = output_embed;  long_memory = queries row;  query_embed = queries row (use_dab) or
+ *     det_embed[r][:C] | queries row.
+ *   next_id grows by the births placed; births beyond the free slots are not placed and are added to counters[b][1];
+ *   counters[b][0] = live slots afterwards.
+ * n_det and cap of any size (chunks of 1024).  No atomics: ranks come from ballots and prefix sums, the same inputs give
+ * the same bits.  Calls on one bank are issued on one stream.  B == 0 launches nothing.  Returns 1 for a bad argument
+ * (negative size or stride, cap < 1, K < 1, C < 1, null pointer), 3 when the launch failed. */
+int clipops_bank_update_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap, int K,
+                            int C, int use_dab, float det_score_thresh, float track_score_thresh,
+                            int64_t miss_tolerance, void *stream);
+
+/* clipops_result_rows_f32 for every stream of a bank in one launch, into one table: the same filters, float32 roundings
+ * and capacity rule; slot (b, s) is offered when ids[b][s] >= 0, streams in order, slots in order.  rows_i is
+ * (capacity, 4): sequence, frame, id, label.  seq_frame int64 (B, 2) = (sequence, frame) and ori_wh float32 (B, 2) =
+ * (ori_w, ori_h) of stream b are device arrays, so the launch is the same every frame.  B * cap == 0 launches nothing.
+ * Returns 1 for a bad argument (negative size, K < 1, null pointer), 3 when the launch failed. */
+int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels,
+                                 int B, int cap, int K, const int64_t *seq_frame, const float *ori_wh,
+                                 float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
+                                 int32_t *counters, int capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ SYMBOLS = {
                                 [c_int, c_void_p], c_int),
     "clipops_handover_fwd_f32": ([c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 4, c_int),
     "clipops_handover_bwd_f32": ([c_void_p] * 4 + [c_int] * 8 + [c_void_p, c_void_p], c_int),
+    "clipops_bank_update_f32": ([c_void_p, c_void_p] + [c_int] * 6 + [c_float, c_float, ctypes.c_int64, c_void_p], c_int),
+    "clipops_bank_result_rows_f32": ([c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p, c_float, c_float] +
+                                     [c_void_p] * 3 + [c_int, c_void_p], c_int),
 }
 
 # clipops_handover_sources / clipops_handover_grads (include/clip_ops_hip.h); the index of a source is its position here
@@ -75,6 +78,21 @@ class HandoverSources(ctypes.Structure):
 
 class HandoverGrads(ctypes.Structure):
     _fields_ = [("ptr", c_void_p * len(HANDOVER_SOURCES))]
+
+
+# clipops_bank / clipops_bank_model (include/clip_ops_hip.h): the fields of a models/track_bank.TrackBank, in order
+BANK_FIELDS = ("ids", "labels", "disappear_time", "boxes", "ref_pts", "logits", "scores", "output_embed", "long_memory",
+               "last_output", "query_embed", "next_id", "counters", "free_list")
+BANK_MODEL = ("pred_logits", "pred_bboxes", "outputs", "last_ref_pts", "queries")
+
+
+class Bank(ctypes.Structure):
+    _fields_ = [(name, c_void_p) for name in BANK_FIELDS]
+
+
+class BankModel(ctypes.Structure):
+    _fields_ = [("ptr", c_void_p * len(BANK_MODEL)), ("batch_stride", c_long * len(BANK_MODEL)),
+                ("row_stride", c_long * len(BANK_MODEL)), ("det_embed", c_void_p), ("det_row_stride", c_long)]
 
 
 lib, check = _cabi.bind("libclip_ops_hip.so", "clipops", SYMBOLS, ABI_VERSION)

@@ -1468,9 +1468,278 @@ __global__ __launch_bounds__(256) void result_rows_kernel(const float *__restric
     }
 }
 
+// ---- track bank (include/clip_ops_hip.h: clipops_bank_*): the online tracker's bookkeeping for B sequences at once,
+//      on fixed-size slot tables -- no row count ever reaches the host ----
+// One workgroup per stream, three phases separated by barriers:
+//   1. the slots that are free when the call begins, in slot order, into the bank's free_list (ballot + population count
+//      inside a wavefront, wave totals through LDS, a running base across chunks of 1024 slots);
+//   2. one wavefront per live slot: refresh from model row n_det + s, age, retire (the row is zeroed);
+//   3. detect rows in chunks of 1024: one thread decides a row's birth and label, the same ballot scheme ranks the born
+//      rows, rank j takes free_list[j]; the (row, slot) pairs of the chunk go through LDS and one wavefront copies a pair.
+// Phases 2 and 3 write disjoint slots (live / free at the start).  Every counter is read before anything is written and
+// written once by one lane with plain stores; no atomics.
+template <int NW>
+__device__ __forceinline__ void bank_ranks(bool flag, int lane, int wave, int *wave_total, int &before, int &total) {
+    const unsigned long long m = __ballot(flag);
+    const int below = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = __popcll(m);
+    __syncthreads();
+    before = below;
+    total = 0;
+    for (int v = 0; v < NW; ++v) {
+        const int t = wave_total[v];
+        before += v < wave ? t : 0;
+        total += t;
+    }
+}
+
+// (16 wavefronts: phase 2 is a chain of dependent loads per slot, and a wavefront walks its slots one after another)
+constexpr int BANK_THREADS = 1024, BANK_WAVES = BANK_THREADS / 64;
+
+__global__ __launch_bounds__(BANK_THREADS) void bank_update_kernel(clipops_bank_model m, clipops_bank bank, int n_det, int cap,
+                                                          int K, int C, int use_dab, float det_thresh,
+                                                          float track_thresh, int64_t miss_tolerance) {
+#pragma clang fp contract(off)
+    __shared__ int wave_total[BANK_WAVES], wave_live[BANK_WAVES], pair_row[BANK_THREADS], pair_slot[BANK_THREADS];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int QW = use_dab ? C : 2 * C;
+    const long bc = (long)b * cap;
+    int64_t *ids = bank.ids + bc, *labels = bank.labels + bc, *dtime = bank.disappear_time + bc;
+    int32_t *free_list = bank.free_list + bc;
+    float *boxes = bank.boxes + bc * 4, *ref_pts = bank.ref_pts + bc * 4;
+    float *logits = bank.logits + bc * K, *scores = bank.scores + bc * K;
+    float *out_embed = bank.output_embed + bc * C, *long_mem = bank.long_memory + bc * C;
+    float *last_out = bank.last_output + bc * C, *query = bank.query_embed + bc * QW;
+    const float *m_logits = m.ptr[CLIPOPS_BK_LOGITS] + b * m.batch_stride[CLIPOPS_BK_LOGITS];
+    const float *m_boxes = m.ptr[CLIPOPS_BK_BOXES] + b * m.batch_stride[CLIPOPS_BK_BOXES];
+    const float *m_out = m.ptr[CLIPOPS_BK_OUTPUTS] + b * m.batch_stride[CLIPOPS_BK_OUTPUTS];
+    const float *m_ref = m.ptr[CLIPOPS_BK_LAST_REF] + b * m.batch_stride[CLIPOPS_BK_LAST_REF];
+    const float *m_query = m.ptr[CLIPOPS_BK_QUERIES] + b * m.batch_stride[CLIPOPS_BK_QUERIES];
+    const long rs_logits = m.row_stride[CLIPOPS_BK_LOGITS], rs_boxes = m.row_stride[CLIPOPS_BK_BOXES];
+    const long rs_out = m.row_stride[CLIPOPS_BK_OUTPUTS], rs_ref = m.row_stride[CLIPOPS_BK_LAST_REF];
+    const long rs_query = m.row_stride[CLIPOPS_BK_QUERIES];
+    const int64_t next0 = bank.next_id[b];
+    const int dropped0 = bank.counters[2 * b + 1];
+
+    // ---- 1. free slots, as they are before this call
+    int n_free = 0;
+    for (int s0 = 0; s0 < cap; s0 += BANK_THREADS) {
+        const int s = s0 + (int)threadIdx.x;
+        const bool is_free = s < cap && ids[s] < 0;
+        int before, total;
+        bank_ranks<BANK_WAVES>(is_free, lane, wave, wave_total, before, total);
+        if (is_free) free_list[n_free + before] = s;
+        n_free += total;
+        __syncthreads();                            // wave_total is written again; ids are written from here on
+    }
+
+    // ---- 2. live slots: one wavefront each (s, id, label and the decision are uniform over the wavefront)
+    int live = 0;
+    for (int s = wave; s < cap; s += BANK_WAVES) {
+        const int64_t id = ids[s], d0 = dtime[s];
+        int64_t lab = labels[s];
+        if (id < 0) continue;
+        const long r = (long)n_det + s;
+        const float *lg = m_logits + r * rs_logits;
+        lab = lab < 0 ? 0 : (lab >= K ? K - 1 : lab);
+        const float own = sigmoidf(lg[lab]);
+        const int64_t d = own < track_thresh ? d0 + 1 : 0;             // (a NaN score does not age the track)
+        if (d >= miss_tolerance) {                                      // retired: the slot holds zeros again
+            for (int c = lane; c < K; c += 64) logits[(long)s * K + c] = 0.f, scores[(long)s * K + c] = 0.f;
+            if (lane < 4) boxes[s * 4L + lane] = 0.f, ref_pts[s * 4L + lane] = 0.f;
+            for (int c = lane; c < C; c += 64)
+                out_embed[(long)s * C + c] = 0.f, long_mem[(long)s * C + c] = 0.f, last_out[(long)s * C + c] = 0.f;
+            for (int c = lane; c < QW; c += 64) query[(long)s * QW + c] = 0.f;
+            if (lane == 0) ids[s] = -1, labels[s] = 0, dtime[s] = 0;
+        } else {
+            for (int c = lane; c < K; c += 64) {
+                const float v = lg[c];
+                logits[(long)s * K + c] = v;
+                scores[(long)s * K + c] = sigmoidf(v);
+            }
+            if (lane < 4) boxes[s * 4L + lane] = m_boxes[r * rs_boxes + lane];
+            for (int c = lane; c < C; c += 64) out_embed[(long)s * C + c] = m_out[r * rs_out + c];
+            if (lane == 0) dtime[s] = d;
+            ++live;
+        }
+    }
+    if (lane == 0) wave_live[wave] = live;
+    __syncthreads();
+
+    // ---- 3. births
+    int born_base = 0;                              // born rows of the chunks before this one
+    for (int c0 = 0; c0 < n_det; c0 += BANK_THREADS) {      // (n_det is uniform: every thread makes every trip)
+        const int r = c0 + (int)threadIdx.x;
+        bool born = false;
+        int label = 0;
+        if (r < n_det) {
+            const float *lg = m_logits + r * rs_logits;
+            float best = sigmoidf(lg[0]);
+            bool nan = best != best;
+            for (int k = 1; k < K; ++k) {           // the lowest index of the maximum
+                const float v = sigmoidf(lg[k]);
+                nan |= v != v;
+                if (v > best) best = v, label = k;
+            }
+            born = !nan && best >= det_thresh;
+        }
+        int before, total;
+        bank_ranks<BANK_WAVES>(born, lane, wave, wave_total, before, total);
+        const int room = n_free > born_base ? n_free - born_base : 0;
+        const int n_pairs = total < room ? total : room;
+        if (born && before < n_pairs) {
+            const int slot = free_list[born_base + before];
+            pair_row[before] = r;
+            pair_slot[before] = slot;
+            ids[slot] = next0 + born_base + before;
+            labels[slot] = label;
+            dtime[slot] = 0;
+        }
+        __syncthreads();
+        for (int p = wave; p < n_pairs; p += BANK_WAVES) {
+            const long row = pair_row[p], s = pair_slot[p];
+            const float *lg = m_logits + row * rs_logits;
+            for (int c = lane; c < K; c += 64) {
+                const float v = lg[c];
+                logits[s * K + c] = v;
+                scores[s * K + c] = sigmoidf(v);
+            }
+            if (lane < 4) {
+                boxes[s * 4 + lane] = m_boxes[row * rs_boxes + lane];
+                ref_pts[s * 4 + lane] = m_ref[row * rs_ref + lane];
+            }
+            for (int c = lane; c < C; c += 64) {
+                const float o = m_out[row * rs_out + c], q = m_query[row * rs_query + c];
+                out_embed[s * C + c] = o;
+                last_out[s * C + c] = o;
+                long_mem[s * C + c] = q;
+                if (use_dab) {
+                    query[s * QW + c] = q;
+                } else {
+                    query[s * QW + c] = m.det_embed[row * m.det_row_stride + c];
+                    query[s * QW + C + c] = q;
+                }
+            }
+        }
+        born_base += total;
+        __syncthreads();                            // wave_total and the pairs are written again by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        const int placed = born_base < n_free ? born_base : n_free;
+        bank.next_id[b] = next0 + placed;
+        int live_after = placed;
+        for (int v = 0; v < BANK_WAVES; ++v) live_after += wave_live[v];
+        bank.counters[2 * b] = live_after;
+        bank.counters[2 * b + 1] = dropped0 + (born_base - placed);
+    }
+}
+
+// clipops_result_rows_f32's filter and arithmetic over the B * cap slots of a bank, streams in order, free slots skipped:
+// one workgroup, so that the rows of all streams land in one table in a fixed order.
+__global__ __launch_bounds__(256) void bank_result_rows_kernel(const float *__restrict__ boxes,
+                                                               const float *__restrict__ scores,
+                                                               const int64_t *__restrict__ ids,
+                                                               const int64_t *__restrict__ labels, int n_slots, int cap,
+                                                               int K, const int64_t *__restrict__ seq_frame,
+                                                               const float *__restrict__ ori_wh, float score_thresh,
+                                                               float area_thresh, float *__restrict__ rows_f,
+                                                               int64_t *__restrict__ rows_i,
+                                                               int32_t *__restrict__ counters, int capacity) {
+    __shared__ int wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stored0 = counters[0], dropped0 = counters[1];
+    int base = 0;
+    for (int c0 = 0; c0 < n_slots; c0 += 256) {
+        const int i = c0 + (int)threadIdx.x;
+        bool keep = false;
+        int b = 0;
+        float s = 0.f, cx = 0.f, cy = 0.f, w = 0.f, h = 0.f, ori_w = 0.f, ori_h = 0.f;
+        if (i < n_slots && ids[i] >= 0) {
+            b = i / cap;
+            ori_w = ori_wh[2 * b], ori_h = ori_wh[2 * b + 1];
+            const float *sc = scores + (long)i * K;
+            s = sc[0];
+            for (int k = 1; k < K; ++k) {           // torch's max: a NaN wins and stays
+                const float v = sc[k];
+                if (v > s || v != v) s = v;
+            }
+            cx = boxes[4L * i], cy = boxes[4L * i + 1], w = boxes[4L * i + 2], h = boxes[4L * i + 3];
+            const float area = __fmul_rn(__fmul_rn(__fmul_rn(w, ori_w), h), ori_h);
+            keep = s > score_thresh && area > area_thresh;
+        }
+        int before, total;
+        bank_ranks<4>(keep, lane, wave, wave_total, before, total);
+        if (keep) {
+            const long pos = (long)stored0 + base + before;
+            if (pos >= 0 && pos < capacity) {
+                const float hw = __fmul_rn(0.5f, w), hh = __fmul_rn(0.5f, h);
+                float *rf = rows_f + pos * 5;
+                rf[0] = __fmul_rn(__fsub_rn(cx, hw), ori_w);
+                rf[1] = __fmul_rn(__fsub_rn(cy, hh), ori_h);
+                rf[2] = __fmul_rn(__fadd_rn(cx, hw), ori_w);
+                rf[3] = __fmul_rn(__fadd_rn(cy, hh), ori_h);
+                rf[4] = s;
+                int64_t *ri = rows_i + pos * 4;
+                ri[0] = seq_frame[2 * b];
+                ri[1] = seq_frame[2 * b + 1];
+                ri[2] = ids[i];
+                ri[3] = labels[i];
+            }
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int room = stored0 < 0 ? 0 : (capacity > stored0 ? capacity - stored0 : 0);
+        const int stored = base < room ? base : room;
+        counters[0] = stored0 + stored;
+        counters[1] = dropped0 + (base - stored);
+    }
+}
+
 extern "C" {
 
 int clipops_abi_version(void) { return CLIPOPS_ABI_VERSION; }
+
+int clipops_bank_update_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap, int K,
+                            int C, int use_dab, float det_score_thresh, float track_score_thresh,
+                            int64_t miss_tolerance, void *stream) {
+    if (B < 0 || n_det < 0 || cap < 0) return fail(1, "clipops_bank_update_f32: negative size");
+    if (K < 1 || C < 1) return fail(1, "clipops_bank_update_f32: K < 1 or C < 1");
+    if (cap < 1) return fail(1, "clipops_bank_update_f32: a bank without slots");
+    if (B == 0) { g_err[0] = 0; return 0; }
+    if (!model || !bank) return fail(1, "clipops_bank_update_f32: null pointer");
+    for (int i = 0; i < CLIPOPS_BK_N_MODEL; ++i) {
+        if (!model->ptr[i]) return fail(1, "clipops_bank_update_f32: null model pointer");
+        if (model->row_stride[i] < 0 || model->batch_stride[i] < 0)
+            return fail(1, "clipops_bank_update_f32: negative stride");
+    }
+    if (!use_dab && (!model->det_embed || model->det_row_stride < 0))
+        return fail(1, "clipops_bank_update_f32: det_embed is required without DAB");
+    if (!bank->ids || !bank->labels || !bank->disappear_time || !bank->boxes || !bank->ref_pts || !bank->logits ||
+        !bank->scores || !bank->output_embed || !bank->long_memory || !bank->last_output || !bank->query_embed ||
+        !bank->next_id || !bank->counters || !bank->free_list)
+        return fail(1, "clipops_bank_update_f32: null bank pointer");
+    hipLaunchKernelGGL(bank_update_kernel, dim3(B), dim3(BANK_THREADS), 0, (hipStream_t)stream, *model, *bank, n_det, cap, K, C,
+                       use_dab, det_score_thresh, track_score_thresh, miss_tolerance);
+    return check_launch("bank_update_kernel") ? 3 : 0;
+}
+
+int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels,
+                                 int B, int cap, int K, const int64_t *seq_frame, const float *ori_wh,
+                                 float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
+                                 int32_t *counters, int capacity, void *stream) {
+    if (B < 0 || cap < 0 || capacity < 0) return fail(1, "clipops_bank_result_rows_f32: negative size");
+    if (K < 1) return fail(1, "clipops_bank_result_rows_f32: K < 1");
+    if ((long)B * cap > 0x7fffffffL) return fail(1, "clipops_bank_result_rows_f32: more than 2^31 - 1 slots");
+    if ((long)B * cap == 0) { g_err[0] = 0; return 0; }
+    if (!boxes || !scores || !ids || !labels || !seq_frame || !ori_wh || !counters ||
+        (capacity > 0 && (!rows_f || !rows_i)))
+        return fail(1, "clipops_bank_result_rows_f32: null pointer");
+    hipLaunchKernelGGL(bank_result_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, boxes, scores, ids, labels,
+                       B * cap, cap, K, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters, capacity);
+    return check_launch("bank_result_rows_kernel") ? 3 : 0;
+}
 
 int clipops_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels, int n,
                             int K, int64_t frame, float ori_w, float ori_h, float score_thresh, float area_thresh,

@@ -979,3 +979,164 @@ def add_layer_norm(x: torch.Tensor, res: torch.Tensor, norm) -> torch.Tensor:
         return _AddLayerNorm.apply(x.float().contiguous(), res.float().contiguous(), norm.weight, norm.bias,
                                    float(norm.eps))
     return norm(x + res)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# track bank (models/track_bank.py; include/clip_ops_hip.h: clipops_bank_*): the online tracker's bookkeeping for B
+# sequences on fixed-size slot tables
+# --------------------------------------------------------------------------------------------------------------
+def _bank_model_tensors(res: dict, bank, use_dab: bool):
+    """The five decoder outputs the bank update reads, (B, n_det + cap, width) each, and det_query_embed (or None)."""
+    named = dict(pred_logits=res["pred_logits"], pred_bboxes=res["pred_bboxes"], outputs=res["outputs"],
+                 last_ref_pts=res["last_ref_pts"], queries=res["aux_outputs"][-1]["queries"])
+    B, cap, K, C = bank.n_streams, bank.cap, bank.num_classes, bank.hidden_dim
+    widths = dict(pred_logits=K, pred_bboxes=4, outputs=C, last_ref_pts=4, queries=C)
+    rows = named["pred_logits"].shape[1] if named["pred_logits"].dim() == 3 else -1
+    n_det = rows - cap
+    if n_det < 0:
+        raise ValueError(f"bank update: {rows} model rows for a bank of {cap} slots")
+    for name, t in named.items():
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, rows, widths[name]) or t.device != bank.ids.device:
+            raise ValueError(f"bank update: {name} has shape {tuple(t.shape)} ({t.dtype}, {t.device}); expected "
+                             f"{(B, rows, widths[name])} float32 on {bank.ids.device}")
+    det = None
+    if not use_dab:
+        det = res["det_query_embed"]
+        if det.dtype != torch.float32 or det.dim() != 2 or det.shape[0] < n_det or det.shape[1] < C:
+            raise ValueError(f"bank update: det_query_embed has shape {tuple(det.shape)} ({det.dtype})")
+    return named, det, n_det
+
+
+def bank_update(res: dict, bank, det_score_thresh: float, track_score_thresh: float, miss_tolerance: int) -> None:
+    """One frame of track management for every stream of ``bank`` (a ``TrackBank``), in place and without a read-back:
+    ``RuntimeTracker.update`` plus the inference branch of ``QueryUpdater.select_active_tracks`` on slot tables (see
+    include/clip_ops_hip.h: clipops_bank_update_f32).  ``res``: the model's outputs for queries ``cat(det, bank slots)``
+    -- pred_logits, pred_bboxes, outputs, last_ref_pts, aux_outputs[-1]["queries"], each (B, n_det + cap, width) with a
+    dense last axis, and det_query_embed without DAB.  CUDA tensors take one launch; CPU tensors run
+    ``bank_update_reference``."""
+    named, det, n_det = _bank_model_tensors(res, bank, bank.use_dab)
+    if not bank.ids.is_cuda:
+        return bank_update_reference(res, bank, det_score_thresh, track_score_thresh, miss_tolerance)
+    L = _lib()
+    model, keep = L.BankModel(), []
+    for i, name in enumerate(L.BANK_MODEL):
+        t = named[name].detach()
+        if t.shape[2] > 1 and t.stride(2) != 1 or t.stride(0) < 0 or t.stride(1) < 0:
+            t = t.contiguous()
+        keep.append(t)
+        model.ptr[i], model.batch_stride[i], model.row_stride[i] = t.data_ptr(), t.stride(0), t.stride(1)
+    if det is not None:
+        det = _rows_dense(det.detach())
+        model.det_embed, model.det_row_stride = det.data_ptr(), det.stride(0)
+    table = L.Bank()
+    for name in L.BANK_FIELDS:
+        t = getattr(bank, name)
+        if not t.is_contiguous():
+            raise RuntimeError(f"bank update: the bank's {name} is not contiguous")
+        setattr(table, name, t.data_ptr())
+    L.check(L.lib.clipops_bank_update_f32(
+        ctypes.byref(model), ctypes.byref(table), bank.n_streams, n_det, bank.cap, bank.num_classes, bank.hidden_dim,
+        int(bank.use_dab), float(det_score_thresh), float(track_score_thresh), int(miss_tolerance), _stream(bank.ids)),
+        "clipops_bank_update_f32")
+
+
+@torch.no_grad()
+def bank_update_reference(res: dict, bank, det_score_thresh: float, track_score_thresh: float,
+                          miss_tolerance: int) -> None:
+    """``bank_update`` as torch selects and index copies, stream by stream (what CPU tensors run; reads row counts)."""
+    named, det, n_det = _bank_model_tensors(res, bank, bank.use_dab)
+    K, C = bank.num_classes, bank.hidden_dim
+    for b in range(bank.n_streams):
+        logits_all, boxes_all, out_all = named["pred_logits"][b], named["pred_bboxes"][b], named["outputs"][b]
+        live = bank.ids[b] >= 0
+        free_slots = (~live).nonzero().squeeze(1)                       # as they are before this call
+        # live slots: refresh, age, retire
+        logits = logits_all[n_det:]
+        scores = logits.sigmoid()
+        own = scores.gather(1, bank.labels[b].clamp(0, K - 1)[:, None]).squeeze(1)
+        aged = torch.where(own < track_score_thresh, bank.disappear_time[b] + 1, torch.zeros_like(bank.disappear_time[b]))
+        keep = live & ~(aged >= miss_tolerance)
+        retire = live & ~keep
+        col, gone = keep[:, None], retire[:, None]
+        bank.disappear_time[b] = torch.where(keep, aged, torch.zeros_like(aged))
+        bank.ids[b] = torch.where(retire, torch.full_like(bank.ids[b], -1), bank.ids[b])
+        bank.labels[b] = torch.where(retire, torch.zeros_like(bank.labels[b]), bank.labels[b])
+        for name, new in (("boxes", boxes_all[n_det:]), ("logits", logits), ("scores", scores),
+                          ("output_embed", out_all[n_det:])):
+            old = getattr(bank, name)[b]
+            getattr(bank, name)[b] = torch.where(col, new, torch.where(gone, torch.zeros_like(old), old))
+        for name in ("ref_pts", "long_memory", "last_output", "query_embed"):
+            old = getattr(bank, name)[b]
+            getattr(bank, name)[b] = torch.where(gone, torch.zeros_like(old), old)
+        # births: the j-th born row takes the j-th free slot
+        det_scores = logits_all[:n_det].sigmoid()
+        if n_det > 0:
+            top = torch.max(det_scores, dim=-1)
+            born = (top.values >= det_score_thresh).nonzero().squeeze(1)
+            label = top.indices
+        else:
+            born, label = free_slots[:0], free_slots[:0]
+        placed = min(int(born.shape[0]), int(free_slots.shape[0]))
+        rows, slots = born[:placed], free_slots[:placed]
+        queries = named["queries"][b][rows]
+        bank.ids[b][slots] = bank.next_id[b] + torch.arange(placed, dtype=torch.int64, device=rows.device)
+        bank.labels[b][slots] = label[rows]
+        bank.disappear_time[b][slots] = 0
+        bank.logits[b][slots] = logits_all[rows]
+        bank.scores[b][slots] = det_scores[rows]
+        bank.boxes[b][slots] = boxes_all[rows]
+        bank.ref_pts[b][slots] = named["last_ref_pts"][b][rows]
+        bank.output_embed[b][slots] = out_all[rows]
+        bank.last_output[b][slots] = out_all[rows]
+        bank.long_memory[b][slots] = queries
+        bank.query_embed[b][slots] = queries if det is None else torch.cat((det[rows][:, :C], queries), dim=-1)
+        bank.next_id[b] += placed
+        bank.counters[b, 0] = int(keep.sum()) + placed
+        bank.counters[b, 1] += int(born.shape[0]) - placed
+
+
+def bank_result_rows(bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float, area_thresh: float,
+                     rows_f: torch.Tensor, rows_i: torch.Tensor, counters: torch.Tensor) -> None:
+    """The reportable rows of every stream's live tracks behind the rows already in the table (``rows_f`` (capacity, 5)
+    float32, ``rows_i`` (capacity, 4) int64: sequence, frame, id, label; ``counters`` (2,) int32: stored, dropped) -- one
+    launch, nothing read back.  ``seq_frame`` int64 (B, 2) and ``ori_wh`` float32 (B, 2) = (ori_w, ori_h) per stream,
+    on the bank's device.  CPU tensors run ``bank_result_rows_reference``."""
+    B, capacity = bank.n_streams, rows_f.shape[0]
+    if (seq_frame.dtype != torch.int64 or tuple(seq_frame.shape) != (B, 2) or ori_wh.dtype != torch.float32
+            or tuple(ori_wh.shape) != (B, 2)):
+        raise ValueError(f"bank result rows: seq_frame {tuple(seq_frame.shape)} {seq_frame.dtype} / ori_wh "
+                         f"{tuple(ori_wh.shape)} {ori_wh.dtype}; expected int64 and float32 of shape {(B, 2)}")
+    if (rows_f.dtype != torch.float32 or rows_i.dtype != torch.int64 or tuple(rows_f.shape) != (capacity, 5)
+            or tuple(rows_i.shape) != (capacity, 4) or counters.dtype != torch.int32 or counters.numel() != 2):
+        raise ValueError("bank result rows: the table is rows_f (capacity, 5) float32, rows_i (capacity, 4) int64, "
+                         "counters (2,) int32")
+    if not bank.ids.is_cuda:
+        return bank_result_rows_reference(bank, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters)
+    for t in (bank.boxes, bank.scores, bank.ids, bank.labels, seq_frame, ori_wh, rows_f, rows_i, counters):
+        if not t.is_contiguous() or t.device != bank.ids.device:
+            raise RuntimeError("bank result rows: every tensor is contiguous and on the bank's device")
+    L = _lib()
+    L.check(L.lib.clipops_bank_result_rows_f32(
+        bank.boxes.data_ptr(), bank.scores.data_ptr(), bank.ids.data_ptr(), bank.labels.data_ptr(), B, bank.cap,
+        bank.num_classes, seq_frame.data_ptr(), ori_wh.data_ptr(), float(score_thresh), float(area_thresh),
+        rows_f.data_ptr(), rows_i.data_ptr(), counters.data_ptr(), capacity, _stream(bank.ids)),
+        "clipops_bank_result_rows_f32")
+
+
+@torch.no_grad()
+def bank_result_rows_reference(bank, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters) -> None:
+    """``bank_result_rows`` through ``results.host_rows``, stream by stream (what CPU tensors run)."""
+    from ..results import host_rows
+    capacity = rows_f.shape[0]
+    for b in range(bank.n_streams):
+        live = bank.ids[b] >= 0
+        seq, frame = (int(v) for v in seq_frame[b])
+        f, i = host_rows(bank.boxes[b][live], bank.scores[b][live], bank.ids[b][live], bank.labels[b][live], frame,
+                         ori_wh[b, 1], ori_wh[b, 0], score_thresh, area_thresh)
+        at, m = int(counters[0]), int(f.shape[0])
+        stored = max(0, min(m, capacity - at))
+        rows_f[at:at + stored] = f[:stored]
+        rows_i[at:at + stored, 0] = seq
+        rows_i[at:at + stored, 1:] = i[:stored]
+        counters[0] += stored
+        counters[1] += m - stored

@@ -204,6 +204,19 @@ class MeMOTR(nn.Module):
         reference_points = self.get_reference_points(tracks).to(device)     # (B, Nd+Nt, 4) logit space
         query_embed = self.get_query_embed(tracks).to(device)               # (B, Nd+Nt, C | 2C)
         query_mask = self.get_query_mask(tracks).to(device)                 # (B, Nd+Nt) bool
+        return self.decode_queries(encoded, reference_points, query_embed, query_mask)
+
+    def decode_queries(self, encoded: dict, reference_points: torch.Tensor, query_embed: torch.Tensor,
+                       query_mask: torch.Tensor) -> dict:
+        """Decoder -> heads over an ``encode_frame`` result for assembled queries: ``reference_points`` (B, Nq, 4) in
+        logit space, ``query_embed`` (B, Nq, C | 2C) and ``query_mask`` (B, Nq) bool, True = not a key, the first
+        ``n_det_queries`` rows of each being the detect queries.  ``decode_frame`` assembles them from TrackInstances; a
+        caller that keeps its tracks in fixed slots (models/track_bank.py) passes ``cat(det, slots)`` and a mask that is
+        True on the free slots -- without the ``_no_padding`` tag, so that the attention honours it."""
+        if torch.is_autocast_enabled() and os.environ.get("MEMOTR_AUTOCAST_DECODER", "0") != "1":
+            enc32 = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in encoded.items()}
+            with torch.autocast(device_type=encoded["memory"].device.type, enabled=False):
+                return self.decode_queries(enc32, reference_points.float(), query_embed.float(), query_mask)
 
         outputs, init_reference, inter_references, inter_queries, refined = self.transformer.decode(
             encoded, query_embed=query_embed, ref_pts=reference_points, query_mask=query_mask, return_boxes=True)

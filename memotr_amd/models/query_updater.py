@@ -85,11 +85,14 @@ class QueryUpdater(nn.Module):
     # ------------------------------------------------------------------ embedding update
     FIELDS = ("logits", "boxes", "ref_pts", "output_embed", "long_memory", "last_output", "query_embed")
 
-    def update_fields(self, logits, boxes, ref_pts, out_embed, long_memory_in, last_output, query_embed, key_mask=None):
+    def update_fields(self, logits, boxes, ref_pts, out_embed, long_memory_in, last_output, query_embed, key_mask=None,
+                      n_streams: int = 1):
         """The update of reference models/query_updater.py:96-158 as a function of the track fields (n rows each):
         returns the new (ref_pts, long_memory, last_output, query_embed).  ``key_mask`` (1, n) bool marks rows that are
         padding (the captured form runs on a padded row count): their keys take no part in the memory attention, and
-        nothing else mixes rows."""
+        nothing else mixes rows.  ``n_streams``: the rows are those of that many sequences, equally many each and one
+        after the other (``update_bank``); the memory attention then runs per sequence, ``key_mask`` (n_streams, n /
+        n_streams)."""
         C = self.hidden_dim
         lam = self.long_memory_lambda
         scores = torch.max(logits_to_scores(logits), dim=1).values
@@ -104,9 +107,10 @@ class QueryUpdater(nn.Module):
         confidence = self.confidence_weight_net(out_embed)
         short_memory = self.short_memory_fusion(torch.cat((confidence * out_embed, last_output), dim=-1))
 
-        q = (short_memory + query_pos)[None]
-        k = (long_memory + query_pos)[None]
-        attn = memory_attention(self.memory_attn, q, k, out_embed[None], key_padding_mask=key_mask)[0]
+        q = (short_memory + query_pos).reshape(n_streams, -1, C)
+        k = (long_memory + query_pos).reshape(n_streams, -1, C)
+        attn = memory_attention(self.memory_attn, q, k, out_embed.reshape(n_streams, -1, C),
+                                key_padding_mask=key_mask).reshape(-1, C)
         tgt = self.memory_ffn(add_layer_norm(out_embed, self.memory_dropout(attn), self.memory_norm))
         query_feat = self.query_feat_ffn(add_layer_norm(long_memory, self.query_feat_dropout(tgt),
                                                         self.query_feat_norm))
@@ -123,6 +127,23 @@ class QueryUpdater(nn.Module):
             new_query = torch.cat((torch.where(pos_col, refreshed, query_embed[:, :C]),
                                    torch.where(pos_col, query_feat, query_embed[:, C:])), dim=-1)
         return ref_pts, new_long_memory, new_last_output, new_query
+
+    BANK_UPDATED = ("ref_pts", "long_memory", "last_output", "query_embed")
+
+    @torch.no_grad()
+    def update_bank(self, bank) -> None:
+        """``update_fields`` on the slot tables of a ``TrackBank`` (models/track_bank.py), all streams at once: row-wise
+        on (B * cap) rows except for the memory attention, which runs per stream with the free slots masked as keys.
+        Only live slots take the result (a select, no index: nothing is read back); free slots keep their zeros, so a
+        stream without a track -- every key masked, the attention undefined -- leaves nothing behind."""
+        B, cap = bank.n_streams, bank.cap
+        live = bank.ids >= 0
+        new = self.update_fields(*(getattr(bank, f).reshape(B * cap, -1) for f in self.FIELDS), key_mask=~live,
+                                 n_streams=B)
+        col = live.reshape(-1, 1)
+        for name, t in zip(self.BANK_UPDATED, new):
+            old = getattr(bank, name)
+            setattr(bank, name, torch.where(col, t, old.reshape(B * cap, -1)).view(old.shape))
 
     def update_tracks_embedding(self, tracks: List[TrackInstances], frame_slot: int = None, clip_key=None):
         for b, t in enumerate(tracks):

@@ -192,3 +192,125 @@ class ResultLog:
             boxes = [[x1, y1, x2 - x1, y2 - y1] for x1, y1, x2, y2 in r.boxes_xyxy[sl].tolist()]
             evaluator.add_tracker_rows(seq, idx + 1, np.asarray(r.ids[sl].tolist(), np.int64),
                                        np.asarray(boxes, np.float64).reshape(-1, 4))
+
+
+BANK_ROW_I = 4                # sequence, frame, id, label
+
+
+class _SequenceRows:
+    """The rows of one sequence of a ``BankResultLog``: what ``ResultLog``'s writers read of a log."""
+
+    def __init__(self, rows: Rows):
+        self._rows = rows
+
+    def read(self) -> Rows:
+        return self._rows
+
+    __len__ = ResultLog.__len__
+    mot_lines = ResultLog.mot_lines
+    _by_frame = ResultLog._by_frame
+    bdd_frames = ResultLog.bdd_frames
+    add_to = ResultLog.add_to
+
+
+class BankResultLog:
+    """``ResultLog`` for sequences tracked side by side (inference_multi.MultiSequenceTracker): one table for all of
+    them, ``rows_i`` (capacity, 4) = sequence, frame, id, label.  ``append`` is one launch of
+    ``clipops_bank_result_rows_f32`` over every stream of a ``TrackBank``; which sequence and frame a stream is at and
+    the size of its images come from two small device arrays, so the launch is the same every frame.  ``read`` sorts
+    each sequence's rows by (frame, id) -- the order of the one-sequence tracker, whose tracks are in birth order."""
+
+    def __init__(self, device, capacity: int = 4096, dataset_name: str = "DanceTrack"):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.dataset_name = dataset_name
+        self.capacity = max(1, int(capacity))
+        self.rows_f = torch.empty((self.capacity, ROW_F), dtype=torch.float32, device=self.device)
+        self.rows_i = torch.empty((self.capacity, BANK_ROW_I), dtype=torch.int64, device=self.device)
+        self.counters = torch.zeros((2,), dtype=torch.int32, device=self.device)
+        self._bound = 0
+        self._rows = None         # {sequence: Rows} of the last read
+
+    def _grow(self, needed: int) -> None:
+        capacity = max(2 * self.capacity, needed)
+        rows_f = torch.empty((capacity, ROW_F), dtype=torch.float32, device=self.device)
+        rows_i = torch.empty((capacity, BANK_ROW_I), dtype=torch.int64, device=self.device)
+        rows_f[:self._bound].copy_(self.rows_f[:self._bound])
+        rows_i[:self._bound].copy_(self.rows_i[:self._bound])
+        if self.device.type == "cuda":
+            stream = torch.cuda.current_stream(self.device)
+            self.rows_f.record_stream(stream)
+            self.rows_i.record_stream(stream)
+        self.rows_f, self.rows_i, self.capacity = rows_f, rows_i, capacity
+
+    @torch.no_grad()
+    def append(self, bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float,
+               area_thresh: float) -> None:
+        """The reportable rows of every stream's live tracks; ``seq_frame`` int64 (B, 2) = (sequence, frame) and
+        ``ori_wh`` float32 (B, 2) = (ori_w, ori_h) of each stream, on the device.  Nothing is read back: the table grows
+        by the number of slots offered."""
+        from .functions.clip_ops import bank_result_rows
+        if bank.ids.device != self.device:
+            raise ValueError(f"track bank on {bank.ids.device}, result log on {self.device}")
+        self._rows = None
+        offered = bank.n_streams * bank.cap
+        if self._bound + offered > self.capacity:
+            self._grow(self._bound + offered)
+        bank_result_rows(bank, seq_frame, ori_wh, score_thresh, area_thresh, self.rows_f, self.rows_i, self.counters)
+        self._bound += offered
+
+    def reset(self) -> None:
+        self.counters.zero_()
+        self._bound, self._rows = 0, None
+
+    def read(self) -> dict:
+        """``{sequence: Rows}`` on the host, each sorted by (frame, id): one packed copy and one event wait."""
+        if self._rows is not None:
+            return self._rows
+        b = self._bound
+        if self.device.type == "cuda":
+            packed = torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
+                                self.rows_f[:b].reshape(-1).view(torch.uint8)))
+            host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            done.synchronize()
+            raw = host.numpy()
+            counters = raw[:8].view(np.int32)
+            rows_i = raw[8:8 + b * BANK_ROW_I * 8].view(np.int64).reshape(b, BANK_ROW_I)
+            rows_f = raw[8 + b * BANK_ROW_I * 8:].view(np.float32).reshape(b, ROW_F)
+        else:
+            counters, rows_i, rows_f = self.counters.numpy(), self.rows_i[:b].numpy(), self.rows_f[:b].numpy()
+        stored, dropped = int(counters[0]), int(counters[1])
+        if dropped != 0:
+            raise RuntimeError(f"result log: {dropped} rows found no room in a table of {self.capacity}")
+        if stored > b:
+            raise RuntimeError(f"result log: {stored} rows stored, {b} offered (counters written from elsewhere?)")
+        rows_i, rows_f = rows_i[:stored], rows_f[:stored]
+        out = {}
+        for seq in np.unique(rows_i[:, 0]).tolist():
+            pick = np.flatnonzero(rows_i[:, 0] == seq)
+            pick = pick[np.lexsort((rows_i[pick, 2], rows_i[pick, 1]))]
+            out[int(seq)] = Rows(rows_i[pick, 1].copy(), rows_i[pick, 2].copy(), rows_i[pick, 3].copy(),
+                                 np.ascontiguousarray(rows_f[pick, :4]), rows_f[pick, 4].copy())
+        self._rows = out
+        return out
+
+    def sequence(self, seq: int) -> _SequenceRows:
+        """The rows of sequence ``seq`` behind ``ResultLog``'s writers (a sequence without a row: an empty log)."""
+        rows = self.read().get(int(seq))
+        if rows is None:
+            rows = Rows(np.zeros((0,), np.int64), np.zeros((0,), np.int64), np.zeros((0,), np.int64),
+                        np.zeros((0, 4), np.float32), np.zeros((0,), np.float32))
+        return _SequenceRows(rows)
+
+    def mot_lines(self, seq: int, dataset_name: str = None) -> List[str]:
+        return self.sequence(seq).mot_lines(self.dataset_name if dataset_name is None else dataset_name)
+
+    def bdd_frames(self, seq: int, image_paths) -> List[dict]:
+        return self.sequence(seq).bdd_frames(image_paths)
+
+    def add_to(self, evaluator, seq: int, name: str, n_frames: int = None) -> None:
+        self.sequence(seq).add_to(evaluator, name, n_frames)

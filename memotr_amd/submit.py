@@ -107,15 +107,52 @@ def _rank_and_world():
     return 0, 1
 
 
+def submit_streams(streams: Optional[int] = None) -> int:
+    """How many sequences ``submit`` tracks side by side: ``streams``, or MEMOTR_SUBMIT_STREAMS, or 1."""
+    n = int(os.environ.get("MEMOTR_SUBMIT_STREAMS", "1")) if streams is None else int(streams)
+    if n < 1:
+        raise ValueError(f"streams must be at least 1, not {n}")
+    return n
+
+
+def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: str, log) -> List[str]:
+    """``submit_sequence`` for many sequences at once: ``tracker`` (an inference_multi.MultiSequenceTracker) runs them
+    in lockstep through ``track_many_logged``, ``log`` (a results.BankResultLog) holds the rows of all of them, and the
+    files are written when the last one ends.  Returns the files' paths, in the order of ``seq_dirs``."""
+    paths = [sequence_frames(dataset, d) for d in seq_dirs]
+    log.reset()
+    counts = tracker.track_many_logged([p if all(_is_jpeg(x) for x in p) else _pixels(p) for p in paths], log)
+    assert counts == [len(p) for p in paths]
+    predict_dir = os.path.join(outputs_dir, "tracker")
+    os.makedirs(predict_dir, exist_ok=True)
+    files = []
+    for i, seq_dir in enumerate(seq_dirs):
+        seq = os.path.basename(os.path.normpath(seq_dir))
+        if dataset == "BDD100K":
+            out = os.path.join(predict_dir, seq + ".json")
+            with open(out, "w", encoding="utf-8") as f:
+                json.dump(log.bdd_frames(i, paths[i]), f)
+        else:
+            out = os.path.join(predict_dir, seq + ".txt")
+            text = "".join(log.mot_lines(i, dataset))
+            with open(out, "w") as f:
+                f.write(text)
+        files.append(out)
+    return files
+
+
 def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
-           tracker_options: Optional[dict] = None) -> List[str]:
+           tracker_options: Optional[dict] = None, streams: Optional[int] = None) -> List[str]:
     """submit_engine.py:187-252.  ``config``: SUBMIT_DIR, SUBMIT_MODEL, SUBMIT_DATA_SPLIT, DATA_ROOT and the inference
     thresholds (DET_SCORE_THRESH, TRACK_SCORE_THRESH, RESULT_SCORE_THRESH, MISS_TOLERANCE, USE_MOTION and the MOTION_*
     keys).  ``train_config`` (DATASET, USE_DAB and the model's keys) defaults to ``<SUBMIT_DIR>/train/config.yaml``;
     ``model`` defaults to ``load_model(train_config, <SUBMIT_DIR>/<SUBMIT_MODEL>)``.  ``tracker_options``: further
     ``SequenceTracker`` arguments (``raw_size``, ``area_thresh``) for every sequence's tracker.  Returns the files this
-    rank wrote, in sequence order."""
+    rank wrote, in sequence order.  ``streams`` (default: MEMOTR_SUBMIT_STREAMS, else 1): above 1, that many of the
+    rank's sequences are tracked side by side (inference_multi.py) and the files are written from one
+    ``BankResultLog``; the rows are those of ``streams=1`` up to float rounding."""
     from .inference import SequenceTracker
+    streams = submit_streams(streams)
     for key in ("SUBMIT_DIR", "SUBMIT_DATA_SPLIT", "DATA_ROOT"):
         if config.get(key) is None:
             raise ValueError(f"{key} must not be None for the submit process")
@@ -139,6 +176,15 @@ def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
         options["side_stream"] = torch.cuda.Stream(device)
     options.update(tracker_options or {})
     directory = split_dir(config["DATA_ROOT"], dataset, split)
+    if streams > 1:
+        from .inference_multi import MultiSequenceTracker
+        from .results import BankResultLog
+        for key in ("motion_lambda", "motion_min_length", "motion_max_length"):
+            options.pop(key)
+        tracker = MultiSequenceTracker(model, n_streams=streams, **options)
+        return submit_sequences(tracker, dataset, [os.path.join(directory, seq) for seq in
+                                                   sequence_names(directory, *_rank_and_world())],
+                                outputs_dir, BankResultLog(device))
     log = ResultLog(device)
     return [submit_sequence(lambda: SequenceTracker(model, **options), dataset,
                             os.path.join(directory, seq), outputs_dir, log)
