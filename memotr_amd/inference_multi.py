@@ -6,8 +6,9 @@ are too small to fill the device.  Independent sequences have no such dependency
 as one batch: the tracks of every sequence live in the fixed slots of a ``TrackBank`` (models/track_bank.py), and a step
 is
 
-    1. one batched upload + resize/normalise            (data/frames.py)
-    2. one batched encode, queued a step ahead on a side stream, two alternating graph slots
+    1. one batched upload + resize/normalise            (data/frames.py; utils.host.PinnedUploader)
+    2. one batched encode, queued a step ahead on a side stream, two alternating graph slots (lookahead.Lookahead:
+       the rules are the one-sequence tracker's, the key is the ``_Step``)
     3. ``MeMOTR.decode_queries`` on cat(detect queries, bank slots), free slots masked as keys
     4. ``clip_ops.bank_update``: refresh, age, retire, births -- one launch for all sequences
     5. ``QueryUpdater.update_bank``
@@ -31,26 +32,21 @@ batch shrinks.  A sequence's results do not depend on which sequences it shared 
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional
 
 import torch
 
 from .data.frames import padded_size, padding_mask, preprocess_frames, target_size
 from .functions import clip_ops
-from .inference import SequenceTracker
+from .inference import bdd_frame_result, mot_lines, pack_tracks, reportable
+from .lookahead import Lookahead, is_stream_like
 from .models.track_bank import TrackBank
 from .models.utils import get_model
 from .structures.track_instances import TrackInstances
+from .utils.host import PinnedUploader, to_host
 from .utils.nested_tensor import NestedTensor
 
 _DONE = object()
-
-
-def _stream_like(item) -> bool:
-    """A JPEG path or byte stream (as ``SequenceTracker.track_annotated`` tells them from decoded frames)."""
-    return isinstance(item, (str, bytes, bytearray, memoryview, os.PathLike)) or \
-        (hasattr(item, "ndim") and item.ndim == 1)
 
 
 class _Step:
@@ -71,7 +67,7 @@ class _Sequence:
 
     @staticmethod
     def _size(item):
-        if not _stream_like(item):
+        if not is_stream_like(item):
             return int(item.shape[0]), int(item.shape[1])
         from .data import jpeg as J
         try:
@@ -104,11 +100,9 @@ class MultiSequenceTracker:
         self.area_thresh, self.use_dab, self.raw_size = area_thresh, use_dab, raw_size
         self.device = next(self.core.parameters()).device
         self.bank: Optional[TrackBank] = None
-        self._pending = None          # (_Step, encode result, event): the next step's encode half, queued ahead
-        self._slot = 0
-        self._side = side_stream
-        self._staging = {}            # (parity, stream) -> [pinned upload buffer, event of its last copy]
-        self._parity = 0
+        self._lookahead = Lookahead(self.model, self.device, side_stream)     # keyed by the _Step
+        self._uploader = PinnedUploader(self.device)      # one pinned buffer per (parity, stream)
+        self._parity = 0              # flipped once per batch upload: a buffer comes round every second step
         self._jpeg_staging = None
         self._counts = [None, None]   # two pinned copies of the bank's counters, each with the event of its copy
         self._counts_i = 0
@@ -121,17 +115,17 @@ class MultiSequenceTracker:
                    result_score_thresh=config["RESULT_SCORE_THRESH"], miss_tolerance=config["MISS_TOLERANCE"],
                    use_dab=config["USE_DAB"], use_motion=config.get("USE_MOTION", False), **options)
 
-    mot_lines = SequenceTracker.mot_lines
-    bdd_frame_result = staticmethod(SequenceTracker.bdd_frame_result)
+    def mot_lines(self, frame_idx: int, tracks: TrackInstances) -> List[str]:
+        return mot_lines(self.dataset_name, frame_idx, tracks)
+
+    bdd_frame_result = staticmethod(bdd_frame_result)
 
     # ------------------------------------------------------------------ the bank
     def begin(self, n_streams: int) -> TrackBank:
         """A fresh bank of ``n_streams`` empty streams (what ``track_many`` starts every geometry group with)."""
         if not 1 <= n_streams <= self.n_streams:
             raise ValueError(f"{n_streams} streams asked of a tracker made for {self.n_streams}")
-        if self._pending is not None and self.device.type == "cuda":
-            torch.cuda.current_stream(self.device).wait_event(self._pending[2])
-        self._pending = None
+        self._lookahead.forget()
         self._counts = [None, None]
         self.bank = TrackBank(n_streams, self.cap, num_classes=self.core.num_classes, hidden_dim=self.core.hidden_dim,
                               use_dab=self.use_dab, device=self.device)
@@ -170,8 +164,9 @@ class MultiSequenceTracker:
         list the next call will pass (the same object), whose upload and encode half are queued on the side stream."""
         if self.bank is None:
             self.begin(len(frames))
-        step = self._pending[0] if self._pending is not None and self._pending[0].source is frames else \
-            _Step(frames, source=frames)
+        step = self._lookahead.pending_key
+        if step is None or step.source is not frames:
+            step = _Step(frames, source=frames)
         sizes = [(int(f.shape[0]), int(f.shape[1])) for f in step.frames]
         ahead = None if next_frames is None else (lambda: _Step(next_frames, source=next_frames))
         self._advance(step, ahead, bgr)
@@ -188,10 +183,7 @@ class MultiSequenceTracker:
         """Steps 1-2: this step's encode result -- the one queued ahead by the previous step, or computed now."""
         if len(step.frames) != self.bank.n_streams:
             raise ValueError(f"{len(step.frames)} frames for a bank of {self.bank.n_streams} streams")
-        pending, self._pending = self._pending, None
-        if pending is not None and self.device.type == "cuda":
-            torch.cuda.current_stream(self.device).wait_event(pending[2])
-        return pending[1] if pending is not None and pending[0] is step else self._encode_batch(step, bgr)
+        return self._lookahead.take(step, lambda s, after: self._batch_frame(s, bgr, after))
 
     @torch.no_grad()
     def _track(self, enc: dict, ahead, bgr: bool) -> Optional[_Step]:
@@ -201,8 +193,9 @@ class MultiSequenceTracker:
         nxt = None
         if ahead is not None:
             nxt = ahead()
-            if nxt is not None and self.device.type == "cuda":
-                self._prefetch(nxt, bgr)
+            if nxt is not None:             # (uploads on the side stream first, then the wait for main)
+                self._lookahead.queue(nxt, lambda s, after: self._batch_frame(s, bgr, after), False,
+                                      inputs=[nxt.batch] + nxt.frames)
         clip_ops.bank_update(res, bank, self.det_score_thresh, self.track_score_thresh, self.miss_tolerance)
         self.core.query_updater.update_bank(bank)
         self._watch_counts()
@@ -227,22 +220,9 @@ class MultiSequenceTracker:
                                    torch.cat((det_mask, bank.query_mask()), dim=1))
 
     # ------------------------------------------------------------------ upload and encode
-    def _upload_into(self, frame, dev: torch.Tensor, key) -> None:
-        """``frame`` (host) into ``dev`` on the current stream, through a pinned buffer of this (parity, stream)."""
-        frame = torch.from_numpy(frame) if not torch.is_tensor(frame) else frame
-        if frame.is_pinned() and frame.is_contiguous():
-            dev.copy_(frame, non_blocking=True)
-            return
-        entry = self._staging.get(key)
-        if entry is None or entry[0].shape != frame.shape:
-            entry = self._staging[key] = [torch.empty(frame.shape, dtype=torch.uint8, pin_memory=True), None]
-        elif entry[1] is not None:
-            entry[1].synchronize()              # the copy out of this buffer two steps ago (long done)
-        entry[0].copy_(frame)
-        dev.copy_(entry[0], non_blocking=True)
-        entry[1] = torch.cuda.current_stream(self.device).record_event()
-
-    def _encode_batch(self, step: _Step, bgr: bool, after=None) -> dict:
+    def _batch_frame(self, step: _Step, bgr: bool, after=None) -> NestedTensor:
+        """Step 1: the frames of ``step`` as the padded normalised batch (``after``: the stream the preprocess kernel
+        waits for once the uploads are queued)."""
         frames = [torch.from_numpy(f) if not torch.is_tensor(f) else f for f in step.frames]
         B = len(frames)
         sizes = {target_size(int(f.shape[0]), int(f.shape[1]), *self.raw_size) for f in frames}
@@ -257,19 +237,12 @@ class MultiSequenceTracker:
                 batch = torch.empty((B,) + tuple(frames[0].shape), dtype=torch.uint8, device=self.device)
                 self._parity ^= 1
                 for b, f in enumerate(frames):
-                    self._upload_into(f, batch[b], (self._parity, b))
+                    self._uploader.into(f, batch[b], (self._parity, b))
             elif not cuda:
                 batch = torch.stack(frames)
         if batch is None and cuda:
             self._parity ^= 1
-            devs = []
-            for b, f in enumerate(frames):
-                if not f.is_cuda:
-                    dev = torch.empty(f.shape, dtype=torch.uint8, device=self.device)
-                    self._upload_into(f, dev, (self._parity, b))
-                    f = dev
-                devs.append(f.to(self.device))
-            frames = devs
+            frames = [self._uploader.upload(f, (self._parity, b)) for b, f in enumerate(frames)]
         if after is not None:                   # (the uploads depend on nothing that stream has queued)
             torch.cuda.current_stream(self.device).wait_stream(after)
         if batch is not None:
@@ -281,32 +254,12 @@ class MultiSequenceTracker:
                 preprocess_frames(f, bgr=bgr, out=out[b:b + 1], size=(th, tw))
             frame = NestedTensor(out, padding_mask(B, th, tw, Hp, Wp, self.device), sizes=((Hp, Wp),) + ((th, tw),) * B)
         step.kept = (batch, frames)             # (device frames stay referenced until the step is done)
-        frame.encode_slot = self._slot
-        frame.encode_static_ok = True
-        self._slot ^= 1
-        return self.model(frame=frame, stage="encode")
-
-    @torch.no_grad()
-    def _prefetch(self, step: _Step, bgr: bool) -> None:
-        main = torch.cuda.current_stream(self.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(self.device)
-        side = self._side
-        with torch.cuda.stream(side):
-            enc = self._encode_batch(step, bgr, after=main)
-            event = side.record_event()
-        for f in ([step.batch] if step.batch is not None else []) + [f for f in step.frames if torch.is_tensor(f)]:
-            if f.is_cuda:
-                f.record_stream(side)
-        for v in enc.values():                  # produced on the side stream, consumed on main
-            if torch.is_tensor(v) and v.is_cuda:
-                v.record_stream(main)
-        self._pending = (step, enc, event)
+        return frame
 
     def _materialise(self, items, bgr: bool, stream=None) -> _Step:
         """The frames of a step from the sources' items: decoded frames as they are; JPEG paths / byte streams through
         ``decode_jpegs`` (host entropy stage now, upload and pixel kernels on ``stream``)."""
-        jpeg = [b for b, x in enumerate(items) if _stream_like(x)]
+        jpeg = [b for b, x in enumerate(items) if is_stream_like(x)]
         if not jpeg:
             return _Step(items)
         from .data import jpeg as J
@@ -326,30 +279,17 @@ class MultiSequenceTracker:
     # ------------------------------------------------------------------ results
     @torch.no_grad()
     def _report_all(self, sizes) -> List[TrackInstances]:
-        """``SequenceTracker._report`` for every stream from ONE packed copy: the live slots of a stream in id order --
+        """``inference.reportable`` for every stream from ONE packed copy: the live slots of a stream in id order --
         the one-sequence tracker's tracks are in birth order."""
-        bank = self.bank
-        B, cap, K = bank.n_streams, bank.cap, bank.num_classes
-        packed = torch.cat((bank.boxes.double(), bank.scores.double(), bank.ids.double()[..., None],
-                            bank.labels.double()[..., None]), dim=2)
-        if packed.is_cuda:
-            host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=True)
-            host.copy_(packed, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            done.synchronize()
-        else:
-            host = packed
+        bank, K = self.bank, self.bank.num_classes
+        host = to_host(pack_tracks(bank.boxes, bank.scores, bank.ids, bank.labels, K))
         out = []
         for b, (ori_h, ori_w) in enumerate(sizes):
             rows = host[b]
             ids = rows[:, 4 + K].long()
             slots = (ids >= 0).nonzero().squeeze(1)
-            rows = rows[slots[torch.argsort(ids[slots])]]
-            t = TrackInstances(hidden_dim=bank.hidden_dim, num_classes=K, use_dab=self.use_dab)
-            t.boxes, t.scores = rows[:, :4].float(), rows[:, 4:4 + K].float()
-            t.ids, t.labels = rows[:, 4 + K].long(), rows[:, 5 + K].long()
-            out.append(SequenceTracker._report(self, t, ori_h, ori_w))
+            out.append(reportable(rows[slots[torch.argsort(ids[slots])]], K, ori_h, ori_w, self.result_score_thresh,
+                                  self.area_thresh, hidden_dim=bank.hidden_dim, num_classes=K, use_dab=self.use_dab))
         return out
 
     # ------------------------------------------------------------------ many sequences
@@ -370,8 +310,7 @@ class MultiSequenceTracker:
         live = [queue.pop(0) for _ in range(min(self.n_streams, len(queue)))]
         bank = self.begin(len(live))
         main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        if main is not None and self._side is None:
-            self._side = torch.cuda.Stream(self.device)
+        side = self._lookahead.side_stream() if main is not None else None
         step = self._materialise([s.item for s in live], bgr, main)
         while live:
             meta = [(s.index, s.frame_idx) for s in live]
@@ -398,9 +337,9 @@ class MultiSequenceTracker:
                     if nxt_live:
                         ops.append(("shrink", len(nxt_live)))
             for s in nxt_live:               # (a JPEG stream's size shows when it is decoded: _encode_batch checks it)
-                if not _stream_like(s.item) and s.size != (int(s.item.shape[0]), int(s.item.shape[1])):
+                if not is_stream_like(s.item) and s.size != (int(s.item.shape[0]), int(s.item.shape[1])):
                     raise ValueError(f"sequence {s.index}: frame {s.frame_idx} has another size than its first frame")
-            ahead = (lambda: self._materialise([s.item for s in nxt_live], bgr, self._side)) if nxt_live else None
+            ahead = (lambda: self._materialise([s.item for s in nxt_live], bgr, side)) if nxt_live else None
             step = self._advance(step, ahead, bgr)
             yield on_step(meta, sizes)
             if ended:

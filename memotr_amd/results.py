@@ -4,7 +4,8 @@
 buffer and an event wait per frame.  A submit run needs none of them per frame -- it needs the rows of the whole
 sequence once.  ``ResultLog`` is that table: ``append`` is one launch of ``clipops_result_rows_f32``
 (include/clip_ops_hip.h: score and area filter, xyxy pixel boxes, ballot compaction onto the end of the table),
-``read`` one synchronisation and one copy.
+``read`` one synchronisation and one copy.  ``BankResultLog`` is the same table for sequences tracked side by side;
+the tables, their growth, ``reset`` and the packed, validated read are ``_RowTable``'s for both.
 
     log = ResultLog(device)
     n_frames = tracker.track_logged(paths, log)
@@ -20,7 +21,10 @@ from typing import List, NamedTuple
 import numpy as np
 import torch
 
+from .utils.host import to_host
+
 ROW_F, ROW_I = 5, 3           # x1, y1, x2, y2, score | frame, id, label
+BANK_ROW_I = 4                # sequence, frame, id, label
 
 
 class Rows(NamedTuple):
@@ -50,9 +54,10 @@ def host_rows(boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labe
     return rows_f, rows_i
 
 
-class ResultLog:
-    """``rows_f`` (capacity, 5) float32, ``rows_i`` (capacity, 3) int64 and ``counters`` (2,) int32 (rows stored, rows
-    dropped for lack of room) on ``device``.  All calls on one log are made on one stream."""
+class _RowTable:
+    """``rows_f`` (capacity, 5) float32, ``rows_i`` (capacity, ``WIDTH_I``) int64 and ``counters`` (2,) int32 (rows
+    stored, rows dropped for lack of room) on ``device``, the bound on the rows in use and the last read.  A log adds
+    ``WIDTH_I``, ``append`` and ``_as_rows``.  All calls on one log are made on one stream."""
 
     def __init__(self, device, capacity: int = 4096):
         self.device = torch.device(device)
@@ -60,17 +65,22 @@ class ResultLog:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.capacity = max(1, int(capacity))
         self.rows_f = torch.empty((self.capacity, ROW_F), dtype=torch.float32, device=self.device)
-        self.rows_i = torch.empty((self.capacity, ROW_I), dtype=torch.int64, device=self.device)
+        self.rows_i = torch.empty((self.capacity, self.WIDTH_I), dtype=torch.int64, device=self.device)
         self.counters = torch.zeros((2,), dtype=torch.int32, device=self.device)
         self._bound = 0           # the rows appended can be no more than the rows offered: known without a read
         self._rows = None         # the last read, until the next append / reset
 
-    # ------------------------------------------------------------------ device side
+    def _make_room(self, offered: int) -> None:
+        """Before an append of at most ``offered`` rows (the caller then adds them to ``_bound``)."""
+        self._rows = None
+        if self._bound + offered > self.capacity:
+            self._grow(self._bound + offered)
+
     def _grow(self, needed: int) -> None:
         """Larger tables and a stream-ordered device copy of the part that may be in use."""
         capacity = max(2 * self.capacity, needed)
         rows_f = torch.empty((capacity, ROW_F), dtype=torch.float32, device=self.device)
-        rows_i = torch.empty((capacity, ROW_I), dtype=torch.int64, device=self.device)
+        rows_i = torch.empty((capacity, self.WIDTH_I), dtype=torch.int64, device=self.device)
         rows_f[:self._bound].copy_(self.rows_f[:self._bound])
         rows_i[:self._bound].copy_(self.rows_i[:self._bound])
         if self.device.type == "cuda":        # the old tables are read by that copy on this stream
@@ -79,60 +89,23 @@ class ResultLog:
             self.rows_i.record_stream(stream)
         self.rows_f, self.rows_i, self.capacity = rows_f, rows_i, capacity
 
-    @torch.no_grad()
-    def append(self, boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labels: torch.Tensor,
-               frame_idx: int, ori_h, ori_w, score_thresh: float, area_thresh: float) -> None:
-        """The reportable rows of one frame's live tracks (``boxes`` (n,4) cxcywh normalised, ``scores`` (n,K) or (n,),
-        ``ids`` / ``labels`` (n,)) behind the rows already there.  Nothing is read back."""
-        n = int(boxes.shape[0])
-        if n == 0:
-            return
-        if boxes.device != self.device:
-            raise ValueError(f"tracks on {boxes.device}, result log on {self.device}")
-        self._rows = None
-        if self._bound + n > self.capacity:
-            self._grow(self._bound + n)
-        if self.device.type != "cuda":
-            rows_f, rows_i = host_rows(boxes, scores, ids, labels, frame_idx, ori_h, ori_w, score_thresh, area_thresh)
-            at, m = int(self.counters[0]), rows_f.shape[0]
-            self.rows_f[at:at + m], self.rows_i[at:at + m] = rows_f, rows_i
-            self.counters[0] += m
-            self._bound += n
-            return
-        from . import _clip_lib as L      # no substitute: a missing library is an error
-        boxes = boxes.detach().float().contiguous()
-        scores = scores.detach().float().reshape(n, -1).contiguous()
-        ids, labels = ids.long().contiguous(), labels.long().contiguous()
-        L.check(L.lib.clipops_result_rows_f32(
-            boxes.data_ptr(), scores.data_ptr(), ids.data_ptr(), labels.data_ptr(), n, scores.shape[1], int(frame_idx),
-            float(ori_w), float(ori_h), float(score_thresh), float(area_thresh), self.rows_f.data_ptr(),
-            self.rows_i.data_ptr(), self.counters.data_ptr(), self.capacity,
-            torch.cuda.current_stream(self.device).cuda_stream), "clipops_result_rows_f32")
-        self._bound += n
-
     def reset(self) -> None:
         """Empty the log for the next sequence (stream-ordered; the tables keep their size)."""
         self.counters.zero_()
         self._bound, self._rows = 0, None
 
-    # ------------------------------------------------------------------ host side
-    def read(self) -> Rows:
-        """The rows on the host: one packed copy through a pinned buffer and one event wait."""
+    def read(self):
+        """The rows on the host (``_as_rows`` of the stored part of the tables): one packed copy through a pinned buffer
+        and one event wait (``utils.host.to_host``)."""
         if self._rows is not None:
             return self._rows
-        b = self._bound
+        b, w = self._bound, self.WIDTH_I
         if self.device.type == "cuda":
-            packed = torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
-                                self.rows_f[:b].reshape(-1).view(torch.uint8)))
-            host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(packed, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            done.synchronize()
-            raw = host.numpy()
+            raw = to_host(torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
+                                     self.rows_f[:b].reshape(-1).view(torch.uint8)))).numpy()
             counters = raw[:8].view(np.int32)
-            rows_i = raw[8:8 + b * ROW_I * 8].view(np.int64).reshape(b, ROW_I)
-            rows_f = raw[8 + b * ROW_I * 8:].view(np.float32).reshape(b, ROW_F)
+            rows_i = raw[8:8 + b * w * 8].view(np.int64).reshape(b, w)
+            rows_f = raw[8 + b * w * 8:].view(np.float32).reshape(b, ROW_F)
         else:
             counters, rows_i, rows_f = self.counters.numpy(), self.rows_i[:b].numpy(), self.rows_f[:b].numpy()
         stored, dropped = int(counters[0]), int(counters[1])
@@ -140,9 +113,18 @@ class ResultLog:
             raise RuntimeError(f"result log: {dropped} rows found no room in a table of {self.capacity}")
         if stored > b:
             raise RuntimeError(f"result log: {stored} rows stored, {b} offered (counters written from elsewhere?)")
-        rows_i, rows_f = rows_i[:stored], rows_f[:stored]
-        self._rows = Rows(rows_i[:, 0].copy(), rows_i[:, 1].copy(), rows_i[:, 2].copy(),
-                          np.ascontiguousarray(rows_f[:, :4]), rows_f[:, 4].copy())
+        self._rows = self._as_rows(rows_i[:stored], rows_f[:stored])
+        return self._rows
+
+
+class _SequenceRows:
+    """The ``Rows`` of one sequence (``read()``) and what is written from them: a sequence of a ``BankResultLog`` as
+    it stands, and the writers of ``ResultLog``, whose ``read`` is the table's."""
+
+    def __init__(self, rows: Rows):
+        self._rows = rows
+
+    def read(self) -> Rows:
         return self._rows
 
     def __len__(self) -> int:
@@ -194,55 +176,58 @@ class ResultLog:
                                        np.asarray(boxes, np.float64).reshape(-1, 4))
 
 
-BANK_ROW_I = 4                # sequence, frame, id, label
+class ResultLog(_RowTable, _SequenceRows):
+    """The table of one sequence: ``rows_i`` = frame, id, label; ``read`` gives ``Rows`` in the order appended."""
+    WIDTH_I = ROW_I
+
+    @torch.no_grad()
+    def append(self, boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labels: torch.Tensor,
+               frame_idx: int, ori_h, ori_w, score_thresh: float, area_thresh: float) -> None:
+        """The reportable rows of one frame's live tracks (``boxes`` (n,4) cxcywh normalised, ``scores`` (n,K) or (n,),
+        ``ids`` / ``labels`` (n,)) behind the rows already there.  Nothing is read back."""
+        n = int(boxes.shape[0])
+        if n == 0:
+            return
+        if boxes.device != self.device:
+            raise ValueError(f"tracks on {boxes.device}, result log on {self.device}")
+        self._make_room(n)
+        if self.device.type != "cuda":
+            rows_f, rows_i = host_rows(boxes, scores, ids, labels, frame_idx, ori_h, ori_w, score_thresh, area_thresh)
+            at, m = int(self.counters[0]), rows_f.shape[0]
+            self.rows_f[at:at + m], self.rows_i[at:at + m] = rows_f, rows_i
+            self.counters[0] += m
+            self._bound += n
+            return
+        from . import _clip_lib as L      # no substitute: a missing library is an error
+        boxes = boxes.detach().float().contiguous()
+        scores = scores.detach().float().reshape(n, -1).contiguous()
+        ids, labels = ids.long().contiguous(), labels.long().contiguous()
+        L.check(L.lib.clipops_result_rows_f32(
+            boxes.data_ptr(), scores.data_ptr(), ids.data_ptr(), labels.data_ptr(), n, scores.shape[1], int(frame_idx),
+            float(ori_w), float(ori_h), float(score_thresh), float(area_thresh), self.rows_f.data_ptr(),
+            self.rows_i.data_ptr(), self.counters.data_ptr(), self.capacity,
+            torch.cuda.current_stream(self.device).cuda_stream), "clipops_result_rows_f32")
+        self._bound += n
+
+    @staticmethod
+    def _as_rows(rows_i, rows_f) -> Rows:
+        return Rows(rows_i[:, 0].copy(), rows_i[:, 1].copy(), rows_i[:, 2].copy(),
+                    np.ascontiguousarray(rows_f[:, :4]), rows_f[:, 4].copy())
 
 
-class _SequenceRows:
-    """The rows of one sequence of a ``BankResultLog``: what ``ResultLog``'s writers read of a log."""
-
-    def __init__(self, rows: Rows):
-        self._rows = rows
-
-    def read(self) -> Rows:
-        return self._rows
-
-    __len__ = ResultLog.__len__
-    mot_lines = ResultLog.mot_lines
-    _by_frame = ResultLog._by_frame
-    bdd_frames = ResultLog.bdd_frames
-    add_to = ResultLog.add_to
-
-
-class BankResultLog:
-    """``ResultLog`` for sequences tracked side by side (inference_multi.MultiSequenceTracker): one table for all of
+class BankResultLog(_RowTable):
+    """The table of sequences tracked side by side (inference_multi.MultiSequenceTracker): one table for all of
     them, ``rows_i`` (capacity, 4) = sequence, frame, id, label.  ``append`` is one launch of
     ``clipops_bank_result_rows_f32`` over every stream of a ``TrackBank``; which sequence and frame a stream is at and
-    the size of its images come from two small device arrays, so the launch is the same every frame.  ``read`` sorts
-    each sequence's rows by (frame, id) -- the order of the one-sequence tracker, whose tracks are in birth order."""
+    the size of its images come from two small device arrays, so the launch is the same every frame.  ``read`` gives
+    ``{sequence: Rows}``, each sequence's rows sorted by (frame, id) -- the order of the one-sequence tracker, whose
+    tracks are in birth order."""
+
+    WIDTH_I = BANK_ROW_I
 
     def __init__(self, device, capacity: int = 4096, dataset_name: str = "DanceTrack"):
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device, capacity)
         self.dataset_name = dataset_name
-        self.capacity = max(1, int(capacity))
-        self.rows_f = torch.empty((self.capacity, ROW_F), dtype=torch.float32, device=self.device)
-        self.rows_i = torch.empty((self.capacity, BANK_ROW_I), dtype=torch.int64, device=self.device)
-        self.counters = torch.zeros((2,), dtype=torch.int32, device=self.device)
-        self._bound = 0
-        self._rows = None         # {sequence: Rows} of the last read
-
-    def _grow(self, needed: int) -> None:
-        capacity = max(2 * self.capacity, needed)
-        rows_f = torch.empty((capacity, ROW_F), dtype=torch.float32, device=self.device)
-        rows_i = torch.empty((capacity, BANK_ROW_I), dtype=torch.int64, device=self.device)
-        rows_f[:self._bound].copy_(self.rows_f[:self._bound])
-        rows_i[:self._bound].copy_(self.rows_i[:self._bound])
-        if self.device.type == "cuda":
-            stream = torch.cuda.current_stream(self.device)
-            self.rows_f.record_stream(stream)
-            self.rows_i.record_stream(stream)
-        self.rows_f, self.rows_i, self.capacity = rows_f, rows_i, capacity
 
     @torch.no_grad()
     def append(self, bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float,
@@ -253,49 +238,19 @@ class BankResultLog:
         from .functions.clip_ops import bank_result_rows
         if bank.ids.device != self.device:
             raise ValueError(f"track bank on {bank.ids.device}, result log on {self.device}")
-        self._rows = None
         offered = bank.n_streams * bank.cap
-        if self._bound + offered > self.capacity:
-            self._grow(self._bound + offered)
+        self._make_room(offered)
         bank_result_rows(bank, seq_frame, ori_wh, score_thresh, area_thresh, self.rows_f, self.rows_i, self.counters)
         self._bound += offered
 
-    def reset(self) -> None:
-        self.counters.zero_()
-        self._bound, self._rows = 0, None
-
-    def read(self) -> dict:
-        """``{sequence: Rows}`` on the host, each sorted by (frame, id): one packed copy and one event wait."""
-        if self._rows is not None:
-            return self._rows
-        b = self._bound
-        if self.device.type == "cuda":
-            packed = torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
-                                self.rows_f[:b].reshape(-1).view(torch.uint8)))
-            host = torch.empty(packed.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(packed, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-            done.synchronize()
-            raw = host.numpy()
-            counters = raw[:8].view(np.int32)
-            rows_i = raw[8:8 + b * BANK_ROW_I * 8].view(np.int64).reshape(b, BANK_ROW_I)
-            rows_f = raw[8 + b * BANK_ROW_I * 8:].view(np.float32).reshape(b, ROW_F)
-        else:
-            counters, rows_i, rows_f = self.counters.numpy(), self.rows_i[:b].numpy(), self.rows_f[:b].numpy()
-        stored, dropped = int(counters[0]), int(counters[1])
-        if dropped != 0:
-            raise RuntimeError(f"result log: {dropped} rows found no room in a table of {self.capacity}")
-        if stored > b:
-            raise RuntimeError(f"result log: {stored} rows stored, {b} offered (counters written from elsewhere?)")
-        rows_i, rows_f = rows_i[:stored], rows_f[:stored]
+    @staticmethod
+    def _as_rows(rows_i, rows_f) -> dict:
         out = {}
         for seq in np.unique(rows_i[:, 0]).tolist():
             pick = np.flatnonzero(rows_i[:, 0] == seq)
             pick = pick[np.lexsort((rows_i[pick, 2], rows_i[pick, 1]))]
             out[int(seq)] = Rows(rows_i[pick, 1].copy(), rows_i[pick, 2].copy(), rows_i[pick, 3].copy(),
                                  np.ascontiguousarray(rows_f[pick, :4]), rows_f[pick, 4].copy())
-        self._rows = out
         return out
 
     def sequence(self, seq: int) -> _SequenceRows:

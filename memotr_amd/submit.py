@@ -66,29 +66,39 @@ def _pixels(paths):
                 yield torch.from_numpy(np.array(im.convert("RGB"), order="C"))
 
 
-def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog) -> str:
-    """Track the sequence in ``seq_dir`` with a fresh tracker from ``tracker_factory()`` and write
-    ``<outputs_dir>/tracker/<seq>.txt`` (BDD100K: ``<seq>.json``) whole, replacing an older file.  ``log`` is emptied
-    first and holds the sequence's rows afterwards.  Returns the file's path."""
+def _source(paths):
+    """What a tracker is given for the frames at ``paths``: the paths themselves when all are JPEG files (decoded on the
+    device), else host-decoded pixels."""
+    return paths if all(_is_jpeg(p) for p in paths) else _pixels(paths)
+
+
+def _write(dataset: str, outputs_dir: str, seq_dir: str, rows, paths) -> str:
+    """``<outputs_dir>/tracker/<seq>.txt`` (BDD100K: ``<seq>.json``) from the rows of one sequence (a ``ResultLog``, or
+    ``BankResultLog.sequence(i)``), written whole, replacing an older file.  Returns the file's path."""
     seq = os.path.basename(os.path.normpath(seq_dir))
-    paths = sequence_frames(dataset, seq_dir)
-    tracker = tracker_factory()
-    log.reset()
-    source = paths if all(_is_jpeg(p) for p in paths) else _pixels(paths)
-    n_frames = tracker.track_logged(source, log)
-    assert n_frames == len(paths)
     predict_dir = os.path.join(outputs_dir, "tracker")
     os.makedirs(predict_dir, exist_ok=True)
     if dataset == "BDD100K":
         out = os.path.join(predict_dir, seq + ".json")
         with open(out, "w", encoding="utf-8") as f:
-            json.dump(log.bdd_frames(paths), f)
+            json.dump(rows.bdd_frames(paths), f)
     else:
         out = os.path.join(predict_dir, seq + ".txt")
-        text = "".join(log.mot_lines(dataset))
+        text = "".join(rows.mot_lines(dataset))
         with open(out, "w") as f:
             f.write(text)
     return out
+
+
+def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog) -> str:
+    """Track the sequence in ``seq_dir`` with a fresh tracker from ``tracker_factory()`` and write its result file
+    (``_write``).  ``log`` is emptied first and holds the sequence's rows afterwards.  Returns the file's path."""
+    paths = sequence_frames(dataset, seq_dir)
+    tracker = tracker_factory()
+    log.reset()
+    n_frames = tracker.track_logged(_source(paths), log)
+    assert n_frames == len(paths)
+    return _write(dataset, outputs_dir, seq_dir, log, paths)
 
 
 def load_model(train_config: dict, checkpoint: str):
@@ -121,24 +131,9 @@ def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: st
     files are written when the last one ends.  Returns the files' paths, in the order of ``seq_dirs``."""
     paths = [sequence_frames(dataset, d) for d in seq_dirs]
     log.reset()
-    counts = tracker.track_many_logged([p if all(_is_jpeg(x) for x in p) else _pixels(p) for p in paths], log)
+    counts = tracker.track_many_logged([_source(p) for p in paths], log)
     assert counts == [len(p) for p in paths]
-    predict_dir = os.path.join(outputs_dir, "tracker")
-    os.makedirs(predict_dir, exist_ok=True)
-    files = []
-    for i, seq_dir in enumerate(seq_dirs):
-        seq = os.path.basename(os.path.normpath(seq_dir))
-        if dataset == "BDD100K":
-            out = os.path.join(predict_dir, seq + ".json")
-            with open(out, "w", encoding="utf-8") as f:
-                json.dump(log.bdd_frames(i, paths[i]), f)
-        else:
-            out = os.path.join(predict_dir, seq + ".txt")
-            text = "".join(log.mot_lines(i, dataset))
-            with open(out, "w") as f:
-                f.write(text)
-        files.append(out)
-    return files
+    return [_write(dataset, outputs_dir, d, log.sequence(i), paths[i]) for i, d in enumerate(seq_dirs)]
 
 
 def submit(config: dict, *, model=None, train_config: Optional[dict] = None,

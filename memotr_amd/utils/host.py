@@ -1,4 +1,5 @@
-"""Host-side environment: the CPU quota of the container.
+"""Host-side environment: the CPU quota of the container, CPU affinity next to the GPU, and the two pinned-memory paths
+between host and device that the trackers and the result logs share (``to_host``, ``PinnedUploader``; at the end).
 
 PyTorch sizes its intra-op thread pool from the machine's core count (128 on the 256-thread EPYC hosts of the MI355X
 boxes) and its OpenMP workers spin after every parallel region.  Inside a container with a CFS quota (16 CPUs on those
@@ -114,3 +115,62 @@ def pin_near_gpu(device_index: int = 0, local_rank: int = 0, n_cpus: int = 2):
         return chosen
     except Exception:       # (no sysfs, an exotic topology, a sandbox that forbids it: speed only)
         return None
+
+
+def to_host(packed):
+    """A packed device tensor on the host: a pinned buffer, ONE non-blocking copy and one event wait (`.to("cpu")` field
+    by field is a blocking copy per field).  A CPU tensor is returned as it is."""
+    import torch
+    if not packed.is_cuda:
+        return packed
+    host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=True)
+    host.copy_(packed, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    done.synchronize()
+    return host
+
+
+class PinnedUploader:
+    """uint8 host frames to ``device`` on the current stream without blocking the host.
+
+    * A frame that is pinned and contiguous is copied as it is, non-blocking.
+    * Anything else (pageable memory blocks the host during a copy) goes through a pinned staging buffer, which is
+      reused only once the event of the last copy out of it is synchronised, and reallocated when the shape changes.
+    * Which buffer: the one of ``key``; without a key, one of two that alternate -- only when a staging buffer is
+      actually used.  The caller's keys decide how early a buffer comes round again.
+    * Frames already on a device pass through (``upload``)."""
+
+    def __init__(self, device):
+        self.device = device
+        self._staging = {}            # key -> [pinned buffer, event of its last copy]
+        self._turn = 0
+
+    def upload(self, frame, key=None):
+        """``frame`` (torch or numpy) on the device; on a CPU device, the frame as a tensor."""
+        import torch
+        frame = torch.from_numpy(frame) if not torch.is_tensor(frame) else frame
+        if self.device.type != "cuda" or frame.device == self.device:
+            return frame
+        if frame.is_cuda:
+            return frame.to(self.device)
+        dev = torch.empty(frame.shape, dtype=torch.uint8, device=self.device)
+        self.into(frame, dev, key)
+        return dev
+
+    def into(self, frame, dev, key=None) -> None:
+        """The host tensor ``frame`` into the device tensor ``dev``."""
+        import torch
+        if frame.is_pinned() and frame.is_contiguous():
+            dev.copy_(frame, non_blocking=True)
+            return
+        if key is None:
+            key, self._turn = self._turn, self._turn ^ 1
+        entry = self._staging.get(key)
+        if entry is None or entry[0].shape != frame.shape:
+            entry = self._staging[key] = [torch.empty(frame.shape, dtype=torch.uint8, pin_memory=True), None]
+        elif entry[1] is not None:
+            entry[1].synchronize()              # the copy out of this buffer one round ago (long done)
+        entry[0].copy_(frame)
+        dev.copy_(entry[0], non_blocking=True)
+        entry[1] = torch.cuda.current_stream(self.device).record_event()

@@ -143,6 +143,31 @@ def test_the_log_grows_and_read_raises_on_dropped_rows():
         log.read()
 
 
+@pytest.mark.parametrize("kind", ["one sequence", "bank"])
+def test_both_logs_share_the_tables_growth_and_the_two_read_errors(kind):
+    from memotr_amd.results import BANK_ROW_I, ROW_I, BankResultLog
+    log, width = (ResultLog("cpu", capacity=4), ROW_I) if kind == "one sequence" else \
+        (BankResultLog("cpu", capacity=4), BANK_ROW_I)
+    rows_i = torch.arange(3 * width).reshape(3, width)
+    rows_i[:, 0] = 0                                            # (frame 0, or sequence 0 of the bank log)
+    rows_f = torch.arange(15, dtype=torch.float32).reshape(3, 5)
+    log.rows_i[:3], log.rows_f[:3], log.counters[0], log._bound = rows_i, rows_f, 3, 3
+    log._make_room(6)                                           # 3 in use + 6 offered > 4: max(2 * 4, 9)
+    assert log.capacity == 9 and tuple(log.rows_i.shape) == (9, width) and tuple(log.rows_f.shape) == (9, 5)
+    assert torch.equal(log.rows_i[:3], rows_i) and torch.equal(log.rows_f[:3], rows_f)
+    got = log.read() if kind == "one sequence" else log.read()[0]
+    assert got.ids.tolist() == rows_i[:, width - 2].tolist() and got.scores.tolist() == rows_f[:, 4].tolist()
+    log.counters[0], log._rows = 5, None
+    with pytest.raises(RuntimeError, match=r"result log: 5 rows stored, 3 offered \(counters written from elsewhere\?\)"):
+        log.read()
+    log.counters[0], log.counters[1] = 3, 2
+    with pytest.raises(RuntimeError, match="result log: 2 rows found no room in a table of 9"):
+        log.read()
+    log.reset()
+    assert log.counters.tolist() == [0, 0] and log.capacity == 9
+    assert len(log) == 0 if kind == "one sequence" else log.read() == {}
+
+
 def test_host_rows_keeps_input_order_and_float32():
     boxes, scores, ids, labels = random_tracks(30, 8, seed=9)
     rows_f, rows_i = host_rows(boxes.double(), scores.double(), ids, labels, 7, 1080, 1920, 0.5, 100)

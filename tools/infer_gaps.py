@@ -90,8 +90,8 @@ def timed(name, fn):
 
 tracker.tracker.update = timed("tracker.update", tracker.tracker.update)
 tracker.core.postprocess_single_frame = timed("postprocess (query updater)", tracker.core.postprocess_single_frame)
-tracker._encoded = timed("encode (or take the queued one)", tracker._encoded)
-tracker._prefetch = timed("queue next encode", tracker._prefetch)
+tracker._lookahead.take = timed("encode (or take the queued one)", tracker._lookahead.take)
+tracker._lookahead.queue = timed("queue next encode", tracker._lookahead.queue)
 for look in (False, True):
     for k in list(seg):
         seg[k] = 0.0
