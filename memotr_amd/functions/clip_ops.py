@@ -24,7 +24,7 @@ def config_key() -> tuple:
     return (os.environ.get("MEMOTR_FUSED_CLIP_OPS", "1"), os.environ.get("MEMOTR_COLSUM_TALL", "1"),
             os.environ.get("MEMOTR_ATTN_KERNELS", "1"), os.environ.get("MEMOTR_FUSED_LN", "1"),
             os.environ.get("MEMOTR_FUSED_SHIFT_RELU", "1"), os.environ.get("MEMOTR_FUSED_LINEAR_BWD", "1"),
-            os.environ.get("MEMOTR_FUSED_LINEAR_FWD", "1"))
+            os.environ.get("MEMOTR_FUSED_LINEAR_FWD", "1"), os.environ.get("MEMOTR_LINEAR_STAGED", "1"))
 
 
 def _lib():
