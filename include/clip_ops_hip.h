@@ -389,6 +389,36 @@ int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const 
                                  float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
                                  int32_t *counters, int capacity, void *stream);
 
+/* ---- the overlay's draw table, made on the device from the tracks where they live ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the bank entries: no entry point changed.)
+ * The int32 table trackdraw_draw_u8 draws from (include/track_draw_hip.h: 16 words a row), for every stream of a bank
+ * in one launch, so that an annotated frame needs no result on the host.  boxes (B, cap, 4) cxcywh normalised, scores
+ * (B, cap, K), ids int64 (B, cap) with -1 a free slot, ori_wh float32 (B, 2) = (ori_w, ori_h) on the device (integers
+ * of at most 65535, which float32 carries exactly); table int32 (B, cap, 16).  One sequence's TrackInstances pass as
+ * B = 1, cap = the number of tracks.
+ *   kept    slot (b, s) is kept when ids >= 0 and it passes clipops_result_rows_f32's filters, the same float32
+ *           operations, each rounded once, in the same order: s = max_k scores > score_thresh and
+ *           ((w * ori_w) * h) * ori_h > area_thresh, both strict, a NaN failing either.  Ids are 0 .. 2^31 - 1: a slot
+ *           with a larger id is NOT kept (the host statement, render.track_table, raises there; a kernel cannot).
+ *   order   the kept slots of a stream fill the first rows of table[b] in ascending id order -- the one-sequence
+ *           tracker's birth order, and the order a pixel's last covering primitive depends on.  Ids are unique within a
+ *           stream; equal ids would keep their slot order.
+ *   row     what render.track_table writes for that id and clipops_result_rows_f32's xyxy box: corners floor(v + 0.5)
+ *           in float32 with NaN -> 0 and a clamp to +-2^24; the colour render.palette_entry(id % 64) from its integer
+ *           formula (bytes swapped for bgr); the text colour by the integer luma rule; the glyph count and the packed
+ *           decimal digits; the tab (6 n - 1) font_scale + 2 wide and 7 font_scale + 2 high above the box, inside it
+ *           when it would leave the frame at the top, shifted left to end at column ori_w - 1 on the right.
+ *   padding every other row of table[b] is 0, 0, -1, -1 and twelve zeros: x2 < x1 draws nothing, tab included, so
+ *           trackdraw_draw_u8(..., table[b], n = cap, ...) is launched with a row count the host knows.
+ * One workgroup per stream; the row of a kept slot is the number of kept slots of its stream with a smaller id, counted
+ * by all-pairs compares over chunks of 1024 slots through LDS.  No atomics: the same inputs give the same bits.  cap of
+ * any size.  B * cap == 0 launches nothing.  Arguments are checked on the host without touching a device: returns 1 for
+ * a negative size, more than 2^31 - 1 slots, K < 1, font_scale outside 1 .. 64 or a null pointer with B * cap > 0; 3 when
+ * the launch failed. */
+int clipops_draw_table_f32(const float *boxes, const float *scores, const int64_t *ids, int B, int cap, int K,
+                           const float *ori_wh, float score_thresh, float area_thresh, int bgr, int font_scale,
+                           int32_t *table, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

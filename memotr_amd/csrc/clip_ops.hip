@@ -1959,9 +1959,155 @@ __global__ __launch_bounds__(256) void bank_result_rows_kernel(const float *__re
     }
 }
 
+// ---- the overlay's draw table from device tracks (include/clip_ops_hip.h: clipops_draw_table_f32) ----
+// One workgroup per stream.  A slot's key is its id when the slot is kept (bank_result_rows_kernel's filter, id below
+// 2^31) and -1 otherwise; the row of a kept slot is the number of kept slots of the stream with a smaller id (equal ids,
+// which a bank never holds, in slot order).  Slots go through in chunks of 1024, one thread each; for every chunk of slots
+// the keys of every chunk pass through LDS and each thread counts the ones below its own -- all pairs, no atomics, and
+// every thread also counts the kept slots of the stream, so the padding rows are known without another pass.
+struct DrawKey {
+    int key;                                        // the id of a kept slot, -1 otherwise
+    float x1, y1, x2, y2;
+};
+
+__device__ __forceinline__ DrawKey draw_table_key(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                  const int64_t *__restrict__ ids, long i, int K, float ori_w,
+                                                  float ori_h, float score_thresh, float area_thresh) {
+    DrawKey r = {-1, 0.f, 0.f, 0.f, 0.f};
+    const int64_t id = ids[i];
+    if (id < 0 || id > 0x7fffffffLL) return r;
+    const float *sc = scores + i * K;
+    float s = sc[0];
+    for (int k = 1; k < K; ++k) {                   // torch's max: a NaN wins and stays
+        const float v = sc[k];
+        if (v > s || v != v) s = v;
+    }
+    const float cx = boxes[4 * i], cy = boxes[4 * i + 1], w = boxes[4 * i + 2], h = boxes[4 * i + 3];
+    const float area = __fmul_rn(__fmul_rn(__fmul_rn(w, ori_w), h), ori_h);
+    if (!(s > score_thresh && area > area_thresh)) return r;
+    const float hw = __fmul_rn(0.5f, w), hh = __fmul_rn(0.5f, h);
+    r.key = (int)id;
+    r.x1 = __fmul_rn(__fsub_rn(cx, hw), ori_w);
+    r.y1 = __fmul_rn(__fsub_rn(cy, hh), ori_h);
+    r.x2 = __fmul_rn(__fadd_rn(cx, hw), ori_w);
+    r.y2 = __fmul_rn(__fadd_rn(cy, hh), ori_h);
+    return r;
+}
+
+// floor(v + 0.5) in float32, NaN -> 0, clamped to +-2^24 (render.track_table)
+__device__ __forceinline__ int draw_table_round(float v) {
+    const float r = floorf(__fadd_rn(v, 0.5f));
+    if (r != r) return 0;
+    return (int)fminf(fmaxf(r, -16777216.f), 16777216.f);
+}
+
+// render.palette_entry(i), i in 0 .. 63, as r | g << 8 | b << 16
+__device__ __forceinline__ int draw_table_palette(int i) {
+    const int hue = (i * 13 % 64) * 24, sector = hue >> 8, f = hue & 255;
+    const int lo = i % 3 == 0 ? 0 : (i % 3 == 1 ? 64 : 112);
+    const int up = lo + (255 - lo) * f / 255, down = lo + (255 - lo) * (255 - f) / 255;
+    int r, g, b;
+    switch (sector) {
+        case 0: r = 255, g = up, b = lo; break;
+        case 1: r = down, g = 255, b = lo; break;
+        case 2: r = lo, g = 255, b = up; break;
+        case 3: r = lo, g = down, b = 255; break;
+        case 4: r = up, g = lo, b = 255; break;
+        default: r = 255, g = lo, b = down; break;
+    }
+    return r | g << 8 | b << 16;
+}
+
+constexpr int DRAW_ROW_WORDS = 16;                  // TRACKDRAW_ROW_WORDS of include/track_draw_hip.h
+
+__global__ __launch_bounds__(BANK_THREADS) void draw_table_kernel(const float *__restrict__ boxes,
+                                                                  const float *__restrict__ scores,
+                                                                  const int64_t *__restrict__ ids, int cap, int K,
+                                                                  const float *__restrict__ ori_wh, float score_thresh,
+                                                                  float area_thresh, int bgr, int font_scale,
+                                                                  int32_t *__restrict__ table) {
+    __shared__ int4 keys4[BANK_THREADS / 4];
+    int *keys = reinterpret_cast<int *>(keys4);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long bc = (long)b * cap;
+    const float ori_w = ori_wh[2 * b], ori_h = ori_wh[2 * b + 1];
+    int32_t *rows = table + bc * DRAW_ROW_WORDS;
+    int total = 0;                                  // kept slots of the stream (every thread counts them all)
+    for (int i0 = 0; i0 < cap; i0 += BANK_THREADS) {             // (cap is uniform: every thread makes every trip)
+        const int i = i0 + tid;
+        DrawKey mine = {-1, 0.f, 0.f, 0.f, 0.f};
+        if (i < cap) mine = draw_table_key(boxes, scores, ids, bc + i, K, ori_w, ori_h, score_thresh, area_thresh);
+        int rank = 0;
+        total = 0;
+        for (int j0 = 0; j0 < cap; j0 += BANK_THREADS) {
+            int kj = mine.key;
+            if (j0 != i0) {
+                const int j = j0 + tid;
+                kj = j < cap ? draw_table_key(boxes, scores, ids, bc + j, K, ori_w, ori_h, score_thresh, area_thresh).key
+                             : -1;
+            }
+            keys[tid] = kj;
+            __syncthreads();
+            const int nj4 = (min(BANK_THREADS, cap - j0) + 3) >> 2;     // (every thread wrote a key: -1 past cap)
+#pragma unroll 4
+            for (int q = 0; q < nj4; ++q) {         // four keys a read: the loop is a chain of LDS latencies otherwise
+                const int4 k4 = keys4[q];
+                const int k[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    total += k[e] >= 0;
+                    rank += k[e] >= 0 && (k[e] < mine.key || (k[e] == mine.key && j0 + 4 * q + e < i));
+                }
+            }
+            __syncthreads();                        // keys is written again by the next chunk
+        }
+        if (mine.key < 0) continue;
+        const int id = mine.key;
+        const int x1 = draw_table_round(mine.x1), y1 = draw_table_round(mine.y1);
+        const int rgb = draw_table_palette(id & 63);
+        const int r = rgb & 255, g = (rgb >> 8) & 255, bl = rgb >> 16;
+        int n_digits = 1;
+        for (int v = id; v >= 10; v /= 10) ++n_digits;
+        unsigned lo_word = 0, hi_word = 0;          // glyph k is the k-th digit from the left
+        for (int k = n_digits - 1, v = id; k >= 0; --k, v /= 10) {
+            const unsigned d = (unsigned)(v % 10);
+            if (k < 8) lo_word |= d << (4 * k);
+            else hi_word |= d << (4 * (k - 8));
+        }
+        const int tab_w = (6 * n_digits - 1) * font_scale + 2, tab_h = 7 * font_scale + 2;
+        const int ty1 = y1 - tab_h >= 0 ? y1 - tab_h : y1;
+        const int tx1 = min(x1, (int)ori_w - tab_w);
+        int32_t *row = rows + (long)rank * DRAW_ROW_WORDS;
+        row[0] = x1, row[1] = y1, row[2] = draw_table_round(mine.x2), row[3] = draw_table_round(mine.y2);
+        row[4] = bgr ? (bl | g << 8 | r << 16) : rgb;
+        row[5] = tx1, row[6] = ty1, row[7] = tx1 + tab_w - 1, row[8] = ty1 + tab_h - 1;
+        row[9] = ((77 * r + 150 * g + 29 * bl) >> 8) >= 128 ? 0 : 0xFFFFFF;
+        row[10] = n_digits, row[11] = (int32_t)lo_word, row[12] = (int32_t)hi_word;
+        row[13] = row[14] = row[15] = 0;
+    }
+    for (int p = total + tid; p < cap; p += BANK_THREADS) {      // the rows that draw nothing: x2 < x1
+        int32_t *row = rows + (long)p * DRAW_ROW_WORDS;
+        for (int k = 0; k < DRAW_ROW_WORDS; ++k) row[k] = (k == 2 || k == 3) ? -1 : 0;
+    }
+}
+
 extern "C" {
 
 int clipops_abi_version(void) { return CLIPOPS_ABI_VERSION; }
+
+int clipops_draw_table_f32(const float *boxes, const float *scores, const int64_t *ids, int B, int cap, int K,
+                           const float *ori_wh, float score_thresh, float area_thresh, int bgr, int font_scale,
+                           int32_t *table, void *stream) {
+    if (B < 0 || cap < 0) return fail(1, "clipops_draw_table_f32: negative size");
+    if (K < 1) return fail(1, "clipops_draw_table_f32: K < 1");
+    if (font_scale < 1 || font_scale > 64) return fail(1, "clipops_draw_table_f32: font_scale outside 1 .. 64");
+    if ((long)B * cap > 0x7fffffffL) return fail(1, "clipops_draw_table_f32: more than 2^31 - 1 slots");
+    if ((long)B * cap == 0) { g_err[0] = 0; return 0; }
+    if (!boxes || !scores || !ids || !ori_wh || !table) return fail(1, "clipops_draw_table_f32: null pointer");
+    hipLaunchKernelGGL(draw_table_kernel, dim3(B), dim3(BANK_THREADS), 0, (hipStream_t)stream, boxes, scores, ids, cap, K,
+                       ori_wh, score_thresh, area_thresh, bgr ? 1 : 0, font_scale, table);
+    return check_launch("draw_table_kernel") ? 3 : 0;
+}
 
 int clipops_bank_update_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap, int K,
                             int C, int use_dab, float det_score_thresh, float track_score_thresh,

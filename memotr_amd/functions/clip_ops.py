@@ -1140,3 +1140,76 @@ def bank_result_rows_reference(bank, seq_frame, ori_wh, score_thresh, area_thres
         rows_i[at:at + stored, 1:] = i[:stored]
         counters[0] += stored
         counters[1] += m - stored
+
+
+def _draw_table_args(boxes, scores, ids, ori_wh, font_scale):
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"draw table: boxes {tuple(boxes.shape)}; expected (B, cap, 4)")
+    B, cap = int(boxes.shape[0]), int(boxes.shape[1])
+    scores = scores[:, :, None] if scores.dim() == 2 else scores
+    if scores.dim() != 3 or tuple(scores.shape[:2]) != (B, cap):
+        raise ValueError(f"draw table: scores {tuple(scores.shape)}; expected {(B, cap, 'K')}")
+    if tuple(ids.shape) != (B, cap) or ids.dtype != torch.int64 or scores.shape[2] < 1:
+        raise ValueError(f"draw table: ids {tuple(ids.shape)} {ids.dtype} / scores {tuple(scores.shape)}; expected int64 "
+                         f"{(B, cap)} and {(B, cap, 'K')}")
+    if tuple(ori_wh.shape) != (B, 2) or ori_wh.dtype != torch.float32:
+        raise ValueError(f"draw table: ori_wh {tuple(ori_wh.shape)} {ori_wh.dtype}; expected float32 {(B, 2)}")
+    if isinstance(font_scale, bool) or not isinstance(font_scale, int) or not 1 <= font_scale <= 64:
+        raise ValueError(f"font_scale {font_scale!r} is not an integer in 1 .. 64")
+    return B, cap, scores
+
+
+@torch.no_grad()
+def draw_table(boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float,
+               area_thresh: float, *, bgr: bool = False, font_scale: int = 1, out: torch.Tensor = None) -> torch.Tensor:
+    """The overlay's int32 draw table (B, cap, 16) from tracks on the device (include/clip_ops_hip.h:
+    clipops_draw_table_f32): the reportable slots of every stream in ascending id order as ``render.track_table`` rows,
+    then padding rows that draw nothing -- one launch, nothing read back.  ``boxes`` (B, cap, 4) cxcywh normalised,
+    ``scores`` (B, cap, K), ``ids`` int64 (B, cap) with -1 a free slot (a ``TrackBank``'s fields, or one sequence's
+    ``TrackInstances`` fields with a leading axis of 1), ``ori_wh`` float32 (B, 2) = (ori_w, ori_h).  ``out``: an int32
+    (B, cap, 16) tensor to write.  CPU tensors run ``draw_table_reference``."""
+    B, cap, scores = _draw_table_args(boxes, scores, ids, ori_wh, font_scale)
+    if out is None:
+        out = torch.empty((B, cap, 16), dtype=torch.int32, device=boxes.device)
+    elif tuple(out.shape) != (B, cap, 16) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"draw table: out must be a contiguous int32 {(B, cap, 16)} tensor")
+    if not boxes.is_cuda:
+        out.copy_(draw_table_reference(boxes, scores, ids, ori_wh, score_thresh, area_thresh, bgr=bgr,
+                                       font_scale=font_scale))
+        return out
+    boxes, scores = boxes.detach().float().contiguous(), scores.detach().float().contiguous()
+    ids, ori_wh = ids.contiguous(), ori_wh.contiguous()
+    for t in (scores, ids, ori_wh, out):
+        if t.device != boxes.device:
+            raise RuntimeError("draw table: every tensor is on the tracks' device")
+    L = _lib()
+    L.check(L.lib.clipops_draw_table_f32(
+        boxes.data_ptr(), scores.data_ptr(), ids.data_ptr(), B, cap, scores.shape[2], ori_wh.data_ptr(),
+        float(score_thresh), float(area_thresh), int(bool(bgr)), font_scale, out.data_ptr(), _stream(boxes)),
+        "clipops_draw_table_f32")
+    return out
+
+
+@torch.no_grad()
+def draw_table_reference(boxes, scores, ids, ori_wh, score_thresh, area_thresh, *, bgr: bool = False,
+                         font_scale: int = 1) -> torch.Tensor:
+    """``draw_table`` as a composition of what exists (what CPU tensors run): ``results.host_rows`` of a stream's live
+    slots, sorted by id, through ``render.track_table``, then the padding rows 0, 0, -1, -1."""
+    import numpy as np
+
+    from ..render import ROW_WORDS, track_table
+    from ..results import host_rows
+    B, cap, scores = _draw_table_args(boxes, scores, ids, ori_wh, font_scale)
+    boxes, scores, ids, ori_wh = boxes.detach().cpu(), scores.detach().cpu(), ids.cpu(), ori_wh.cpu()
+    table = np.zeros((B, cap, ROW_WORDS), dtype=np.int32)
+    table[:, :, 2:4] = -1
+    for b in range(B):
+        live = ids[b] >= 0
+        ori_w, ori_h = float(ori_wh[b, 0]), float(ori_wh[b, 1])
+        rows_f, rows_i = host_rows(boxes[b][live], scores[b][live], ids[b][live], torch.zeros_like(ids[b][live]), 0,
+                                   ori_h, ori_w, score_thresh, area_thresh)
+        order = torch.argsort(rows_i[:, 1], stable=True)
+        m = int(order.shape[0])
+        table[b, :m] = track_table(rows_i[order, 1], rows_f[order, :4], int(ori_w), int(ori_h), bgr=bgr,
+                                   font_scale=font_scale)
+    return torch.from_numpy(table)

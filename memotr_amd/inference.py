@@ -297,6 +297,45 @@ class SequenceTracker:
             n = idx + 1
         return n
 
+    def track_annotated_logged(self, source, writer_or_sink, log, *, bgr: bool = False, sequence: int = 0) -> int:
+        """``track_logged`` with the annotated files of ``track_annotated``, and no result on the host: per frame one
+        ``clip_ops.draw_table`` launch makes the overlay's table from ``self.tracks[0]`` (a bank of one stream with as
+        many slots as there are tracks -- the host knows that number) and a ``render.MultiAnnotatedWriter`` draws and
+        encodes behind it.  ``writer_or_sink``: such a writer (the caller closes it; its files are those of sequence
+        ``sequence``), or a callable ``sink(frame_idx, data)`` behind a writer of default options made and closed here.
+        Returns the number of frames."""
+        from .functions.clip_ops import draw_table
+        from .render import MultiAnnotatedWriter
+        own = None
+        if isinstance(writer_or_sink, MultiAnnotatedWriter):
+            writer = writer_or_sink
+        elif callable(writer_or_sink):
+            writer = own = MultiAnnotatedWriter(lambda seq, idx, data: writer_or_sink(idx, data))
+        else:
+            raise TypeError("track_annotated_logged takes a render.MultiAnnotatedWriter or a sink(frame_idx, data)")
+        sizes = {}                    # (ori_w, ori_h) -> the (1, 2) float32 array on the device
+        n = 0
+        try:
+            for idx, cur, nxt in self._frames(source, bgr, on_device=True):
+                self._advance_raw(cur, nxt, bgr)
+                t = self.tracks[0]
+                ori_h, ori_w = int(cur.shape[0]), int(cur.shape[1])
+                log.append(t.boxes, t.scores, t.ids, t.labels, idx, ori_h, ori_w, self.result_score_thresh,
+                           self.area_thresh)
+                ori_wh = sizes.get((ori_w, ori_h))
+                if ori_wh is None:
+                    host = torch.tensor([[ori_w, ori_h]], dtype=torch.float32)
+                    host = host.pin_memory() if self.device.type == "cuda" else host
+                    ori_wh = sizes[(ori_w, ori_h)] = host.to(self.device, non_blocking=True)
+                table = draw_table(t.boxes[None], t.scores[None], t.ids.long()[None], ori_wh, self.result_score_thresh,
+                                   self.area_thresh, bgr=bgr, font_scale=writer.font_scale)
+                writer.add_step([(sequence, idx)], [cur], table, bgr=bgr)
+                n = idx + 1
+        finally:
+            if own is not None:
+                own.close()
+        return n
+
     def mot_lines(self, frame_idx: int, tracks: TrackInstances) -> List[str]:
         return mot_lines(self.dataset_name, frame_idx, tracks)
 

@@ -26,6 +26,9 @@ at one step late; when one passes half the capacity, the bank grows.
     n_frames = tracker.track_many_logged(sources, log)            # no host result per frame
     lines_b = log.mot_lines(1)
 
+    with MultiAnnotatedWriter("annotated/") as writer:            # render.py: an annotated JPEG per frame and sequence,
+        tracker.track_many_annotated_logged(sources, writer, log)  # drawn from a table made on the device
+
 Sequences that share a step share the resized geometry, so they are grouped by ``target_size``; when a sequence ends its
 stream takes the next one of that geometry, and when none is left the last stream's tracks move into the hole and the
 batch shrinks.  A sequence's results do not depend on which sequences it shared steps with, beyond float rounding.
@@ -107,6 +110,9 @@ class MultiSequenceTracker:
         self._counts = [None, None]   # two pinned copies of the bank's counters, each with the event of its copy
         self._counts_i = 0
         self._det_parts = {}          # B -> (reference points, query embeddings, mask) of the detect queries
+        self._done_step = None        # the _Step whose tracks the bank holds
+        self._table = None            # the draw table of the annotated forms, (B, cap, 16) int32: made anew when (B, cap)
+        self._table_read = None       # changes; the event behind the writer's draw launches that read it
 
     @classmethod
     def from_config(cls, model, config: dict, n_streams: int = 4, cap: int = 128, **options):
@@ -340,6 +346,7 @@ class MultiSequenceTracker:
                 if not is_stream_like(s.item) and s.size != (int(s.item.shape[0]), int(s.item.shape[1])):
                     raise ValueError(f"sequence {s.index}: frame {s.frame_idx} has another size than its first frame")
             ahead = (lambda: self._materialise([s.item for s in nxt_live], bgr, side)) if nxt_live else None
+            self._done_step = step          # (its device frames: what an annotating on_step draws into)
             step = self._advance(step, ahead, bgr)
             yield on_step(meta, sizes)
             if ended:
@@ -364,13 +371,61 @@ class MultiSequenceTracker:
         """``track_many`` with the reportable rows of every step appended to ``log`` (results.BankResultLog) on the
         device instead of being brought to the host: one launch per step.  Returns the frame count of every source."""
         def append(meta, sizes):
-            host = torch.tensor([[seq, idx, w, h] for (seq, idx), (h, w) in zip(meta, sizes)], dtype=torch.int64)
-            if self.device.type == "cuda":
-                host = host.pin_memory()
-            dev = host.to(self.device, non_blocking=True)
-            log.append(self.bank, dev[:, :2].contiguous(), dev[:, 2:].float().contiguous(), self.result_score_thresh,
-                       self.area_thresh)
+            seq_frame, ori_wh = self._step_arrays(meta, sizes)
+            log.append(self.bank, seq_frame, ori_wh, self.result_score_thresh, self.area_thresh)
 
         for _ in self._run(sources, bgr, append):
+            pass
+        return list(self.frame_counts)
+
+    def _step_arrays(self, meta, sizes):
+        """``(seq_frame int64 (B, 2), ori_wh float32 (B, 2))`` of a step on the device: one non-blocking upload."""
+        host = torch.tensor([[seq, idx, w, h] for (seq, idx), (h, w) in zip(meta, sizes)], dtype=torch.int64)
+        if self.device.type == "cuda":
+            host = host.pin_memory()
+        dev = host.to(self.device, non_blocking=True)
+        return dev[:, :2].contiguous(), dev[:, 2:].float().contiguous()
+
+    # ------------------------------------------------------------------ annotated output
+    @torch.no_grad()
+    def _annotate(self, writer, meta, ori_wh, bgr: bool) -> None:
+        """One ``clip_ops.draw_table`` launch from the bank and the step's device frames (``_batch_frame`` kept them:
+        no second upload) to ``writer.add_step``.  The table is rewritten only behind the draw launches that read the
+        last one: the current stream waits for their event, the host for nothing."""
+        bank = self.bank
+        shape = (bank.n_streams, bank.cap, 16)
+        if self._table is None or tuple(self._table.shape) != shape:
+            self._table = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif self._table_read is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._table_read)
+        clip_ops.draw_table(bank.boxes, bank.scores, bank.ids, ori_wh, self.result_score_thresh, self.area_thresh,
+                            bgr=bgr, font_scale=writer.font_scale, out=self._table)
+        batch, frames = self._done_step.kept
+        self._table_read = writer.add_step(meta, batch if batch is not None else frames, self._table, bgr=bgr)
+
+    def track_many_annotated(self, sources, writer, *, bgr: bool = False):
+        """``track_many`` with an annotated JPEG per frame and sequence on the side (render.MultiAnnotatedWriter):
+        yields exactly what ``track_many`` yields.  The overlay does not come from the yielded results: per step one
+        launch makes the draw table from the bank, and the writer draws into the device frames the tracker already
+        holds.  ``bgr`` is the frames' channel order, for the model and the writer alike.  The caller closes the
+        writer."""
+        def on_step(meta, sizes):
+            self._annotate(writer, meta, self._step_arrays(meta, sizes)[1], bgr)
+            return meta, self._report_all(sizes)
+
+        for meta, results in self._run(sources, bgr, on_step):
+            for (seq, frame_idx), result in zip(meta, results):
+                yield seq, frame_idx, result
+
+    def track_many_annotated_logged(self, sources, writer, log, *, bgr: bool = False) -> List[int]:
+        """``track_many_logged`` with the annotated files of ``track_many_annotated``: the rows go to ``log`` and the
+        draw table to ``writer`` on the device, and no per-frame result reaches the host.  Returns the frame count of
+        every source."""
+        def on_step(meta, sizes):
+            seq_frame, ori_wh = self._step_arrays(meta, sizes)
+            log.append(self.bank, seq_frame, ori_wh, self.result_score_thresh, self.area_thresh)
+            self._annotate(writer, meta, ori_wh, bgr)
+
+        for _ in self._run(sources, bgr, on_step):
             pass
         return list(self.frame_counts)

@@ -4,6 +4,8 @@ which draws, encodes (data/jpeg_write.py) and writes a JPEG per frame behind the
     out = draw_tracks(frame_u8, result.ids, result.boxes)            # or draw_tracks(frame_u8, result)
     with AnnotatedWriter("out/", quality=90) as writer:
         for idx, result in tracker.track_annotated(frames, writer): ...
+    with MultiAnnotatedWriter("out/", names=["a", "b"]) as writer:   # no result on the host: the table is made on the
+        multi_tracker.track_many_annotated_logged(sources, writer, log)  # device (functions/clip_ops.py: draw_table)
 
 The drawing is ONE definition in integers with two statements that agree to the bit: ``draw_tracks_host`` below in
 numpy (what a CPU tensor takes) and the kernel of csrc/track_draw.hip (what a CUDA tensor takes, one launch on the
@@ -258,6 +260,27 @@ def draw_table_device(frame: torch.Tensor, table: np.ndarray, thickness: int = 2
     return out
 
 
+def draw_resident_table(frame: torch.Tensor, table: torch.Tensor, out: torch.Tensor, thickness: int = 2,
+                        font_scale: int = 1, fill_alpha: int = 0) -> torch.Tensor:
+    """``draw_table_device`` for a table that is already on the device (``clip_ops.draw_table``: (n, 16) int32,
+    contiguous, padding rows included): one launch on the current stream, no upload."""
+    L = _lib()
+    H, W, _ = frame.shape
+    _check_device_frame(frame, "frame_u8")
+    _check_device_frame(out, "out")
+    if (table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != ROW_WORDS or not table.is_contiguous()
+            or table.device != frame.device or out.device != frame.device or tuple(out.shape) != (H, W, 3)):
+        raise ValueError("a resident table is contiguous int32 (n, 16) on the frame's device, out has the frame's shape")
+    n = int(table.shape[0])
+    pitch = lambda t: t.stride(0) if H > 1 else 3 * W  # noqa: E731
+    with torch.cuda.device(frame.device):
+        L.check(L.lib.trackdraw_draw_u8(frame.data_ptr(), pitch(frame), out.data_ptr(), pitch(out), W, H,
+                                        table.data_ptr() if n else None, n, int(thickness), int(font_scale),
+                                        int(fill_alpha), torch.cuda.current_stream(frame.device).cuda_stream),
+                "trackdraw_draw_u8")
+    return out
+
+
 def draw_tracks(frame_u8, ids, boxes_xyxy=None, labels=None, *, bgr: bool = False, thickness: int = 2,
                 font_scale: int = 1, fill_alpha: int = 0, out=None):
     """The tracks of a frame drawn into it.  ``frame_u8``: (H, W, 3) uint8, torch on CPU or GPU (rows may be pitched);
@@ -425,3 +448,162 @@ class AnnotatedWriter:
         self._pool.shutdown(wait=True)
         if self._error is not None:
             raise self._error
+
+
+class MultiAnnotatedWriter(AnnotatedWriter):
+    """``AnnotatedWriter`` for sequences tracked side by side, fed from the device: a step's frames and the draw tables
+    ``clip_ops.draw_table`` made from the tracks where they live -- no result reaches the host.
+
+    ``add_step(meta, frames, tables)``: ``meta[b] = (sequence, frame_idx)`` of stream b; ``frames`` one (B, H, W, 3)
+    uint8 tensor or a list of B (H, W, 3) tensors; ``tables`` int32 (B, cap, 16).  On the writer's side stream, behind
+    the current one: a draw launch per stream into one (n, H, W, 3) buffer per frame size (frames of different sizes in
+    one step are encoded per size: ``encode_jpegs``' rule), one batched encode and one non-blocking download per size
+    into one of three rotating pinned buffers (``AnnotatedWriter``'s rule: written again only after its copy's event and
+    its worker job).  One worker then waits for the event, runs the Huffman stage of the step's frames on
+    ``min(threads, frames, 16)`` host threads (never sized by the CPU count) and hands every file to the sink.  Nothing
+    in ``add_step`` waits for the GPU.  It returns the event behind the draw launches (None on the CPU): whoever rewrites
+    ``tables`` makes its stream wait for it first.  CPU frames (with CPU tables) are drawn and encoded by the host
+    statements on the worker.
+
+    ``out``: a directory -- files are ``<out>/<names[sequence]>/<name.format(frame_idx)>``, ``names`` defaulting to the
+    sequence indices -- or a callable ``sink(sequence, frame_idx, data)``.  ``close()`` drains and re-raises the first
+    worker error; it is idempotent, and the writer is a context manager."""
+
+    def __init__(self, out, names=None, quality: int = 75, subsampling: str = "4:2:0", name: str = "{:08d}.jpg",
+                 threads: int = 4, **draw_options):
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        from .data import jpeg_write as JW
+        unknown = set(draw_options) - {"bgr", "thickness", "font_scale", "fill_alpha"}
+        if unknown:
+            raise TypeError(f"unknown draw options {sorted(unknown)}")
+        JW.quant_tables(quality), JW._hmax(subsampling)
+        if int(threads) < 1:
+            raise ValueError("threads must be at least 1")
+        self.bgr = bool(draw_options.pop("bgr", False))
+        self.thickness, self.font_scale = draw_options.get("thickness", 2), draw_options.get("font_scale", 1)
+        self.fill_alpha = draw_options.get("fill_alpha", 0)
+        _check_options(self.thickness, self.font_scale, self.fill_alpha)
+        self.quality, self.subsampling, self.name, self.threads = quality, subsampling, name, int(threads)
+        self.draw_options = draw_options
+        self.names = None if names is None else [str(n) for n in names]
+        if callable(out):
+            self._sink = out
+        else:
+            self._out, self._made = os.fspath(out), set()
+            os.makedirs(self._out, exist_ok=True)
+            self._sink = self._to_directory
+        self.paths = []                 # files written, in order (directory sinks)
+        self._pool = ThreadPoolExecutor(max_workers=1)
+        self._jobs = []
+        self._slots = [None] * self.SLOTS               # per pinned buffer: [tensor, event, job]
+        self._i = 0
+        self._stream = None
+        self._buffers = {}              # (H, W, n, device) -> (drawn, coef, packed, planes), used on the side stream
+        self._error = None
+        self._closed = False
+
+    def _to_directory(self, seq: int, frame_idx: int, data: bytes) -> None:
+        import os
+        d = os.path.join(self._out, str(seq) if self.names is None else self.names[seq])
+        if d not in self._made:
+            os.makedirs(d, exist_ok=True)
+            self._made.add(d)
+        self._write(os.path.join(d, self.name.format(frame_idx)), data)
+
+    def add(self, *args, **kwargs):
+        raise TypeError("a MultiAnnotatedWriter takes whole steps: add_step(meta, frames, tables)")
+
+    def _step_on_host(self, meta, frames, tables, bgr: bool) -> None:
+        from .data import jpeg_write as JW
+        if tables.is_cuda:
+            raise ValueError("CPU frames are drawn from a CPU table")
+        frames = [f.clone() for f in frames]
+        tables = tables.clone().numpy()
+
+        def on_host():
+            for (seq, idx), frame, table in zip(meta, frames, tables):
+                draw_table_host(frame.numpy(), table, self.thickness, self.font_scale, self.fill_alpha)
+                self._sink(seq, idx, JW.encode_jpeg(frame, self.quality, self.subsampling, bgr))
+
+        self._jobs.append(self._pool.submit(self._run, on_host))
+
+    def add_step(self, meta, frames, tables, *, bgr: Optional[bool] = None):
+        if self._closed:
+            raise RuntimeError("add_step() on a closed MultiAnnotatedWriter")
+        from .data import jpeg_write as JW
+        from .data.jpeg import QT_WORDS
+        bgr = self.bgr if bgr is None else bool(bgr)
+        meta = [(int(seq), int(idx)) for seq, idx in meta]
+        whole = frames if torch.is_tensor(frames) else None
+        frames = [f if torch.is_tensor(f) else torch.from_numpy(f) for f in frames]
+        B = len(meta)
+        if len(frames) != B or tables.dim() != 3 or tables.shape[0] != B or tables.shape[2] != ROW_WORDS \
+                or tables.dtype != torch.int32:
+            raise ValueError(f"a step is {B} (sequence, frame) pairs, {B} frames and an int32 ({B}, cap, 16) table")
+        for f in frames:
+            if f.dim() != 3 or f.shape[2] != 3 or f.dtype != torch.uint8:
+                raise ValueError("a frame is (H, W, 3) uint8")
+        if B == 0:
+            return None
+        if not any(f.is_cuda for f in frames):
+            self._step_on_host(meta, frames, tables, bgr)
+            return None
+        device = tables.device
+        if not all(f.device == device for f in frames) or not tables.is_contiguous():
+            raise ValueError("the frames of a step and its contiguous table are on one device")
+        groups = {}
+        for b, f in enumerate(frames):
+            groups.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(b)
+        infos = {size: JW.frame_info(size[0], size[1], self.subsampling) for size in groups}
+        words = sum(len(idx) * (infos[size].coef_count + QT_WORDS) for size, idx in groups.items())
+        entry = self._take(words)
+        jobs, at = [], 0
+        with torch.cuda.device(device):
+            if self._stream is None or self._stream.device != device:
+                self._stream = torch.cuda.Stream(device)
+            side = self._stream
+            side.wait_stream(torch.cuda.current_stream(device))         # behind the frames' and the table's producers
+            with torch.cuda.stream(side):
+                for (H, W), idx in groups.items():
+                    info, n = infos[(H, W)], len(idx)
+                    row = info.coef_count + QT_WORDS
+                    key = (H, W, n, device)
+                    if key not in self._buffers:                        # (all used on this one stream, in order)
+                        packed = torch.empty((n, row), dtype=torch.int16, device=device)
+                        qt = torch.from_numpy(JW.quant_tables(self.quality).astype(np.int16).reshape(-1))
+                        packed[:, info.coef_count:] = qt.to(device)
+                        self._buffers[key] = (torch.empty((n, H, W, 3), dtype=torch.uint8, device=device),
+                                              torch.empty((n, info.coef_count), dtype=torch.int16, device=device),
+                                              packed, torch.empty(n * info.coef_count, dtype=torch.uint8, device=device))
+                    drawn, coef, packed, planes = self._buffers[key]
+                    for k, b in enumerate(idx):
+                        draw_resident_table(frames[b], tables[b], drawn[k], self.thickness, self.font_scale,
+                                            self.fill_alpha)
+                    jobs.append((idx, info, at))
+                    at += n * row
+                read = side.record_event()                              # the table may be rewritten behind this
+                for (idx, info, start), (H, W) in zip(jobs, groups):
+                    n = len(idx)
+                    drawn, coef, packed, planes = self._buffers[(H, W, n, device)]
+                    JW.forward_coefficients_device(drawn, self.quality, self.subsampling, bgr, out=coef, planes=planes)
+                    packed[:, :info.coef_count].copy_(coef)
+                    entry[0][start:start + packed.numel()].copy_(packed.reshape(-1), non_blocking=True)
+                event = side.record_event()
+            for f in ([whole] if whole is not None else frames):
+                f.record_stream(side)
+            tables.record_stream(side)
+        entry[1] = event
+        host = entry[0]
+
+        def on_worker():
+            event.synchronize()
+            for idx, info, start in jobs:
+                row = info.coef_count + QT_WORDS
+                rows = host[start:start + len(idx) * row].view(len(idx), row)
+                for b, data in zip(idx, JW._huffman_batch(rows, info, min(self.threads, len(idx), 16))):
+                    self._sink(meta[b][0], meta[b][1], data)
+
+        entry[2] = self._pool.submit(self._run, on_worker)
+        self._jobs.append(entry[2])
+        return read

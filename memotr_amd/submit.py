@@ -90,13 +90,19 @@ def _write(dataset: str, outputs_dir: str, seq_dir: str, rows, paths) -> str:
     return out
 
 
-def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog) -> str:
+def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog,
+                    annotate=None) -> str:
     """Track the sequence in ``seq_dir`` with a fresh tracker from ``tracker_factory()`` and write its result file
-    (``_write``).  ``log`` is emptied first and holds the sequence's rows afterwards.  Returns the file's path."""
+    (``_write``).  ``log`` is emptied first and holds the sequence's rows afterwards.  ``annotate``: ``(writer, i)`` --
+    a render.MultiAnnotatedWriter that is also given the annotated frames, as those of its sequence ``i``
+    (``track_annotated_logged``).  Returns the file's path."""
     paths = sequence_frames(dataset, seq_dir)
     tracker = tracker_factory()
     log.reset()
-    n_frames = tracker.track_logged(_source(paths), log)
+    if annotate is None:
+        n_frames = tracker.track_logged(_source(paths), log)
+    else:
+        n_frames = tracker.track_annotated_logged(_source(paths), annotate[0], log, sequence=annotate[1])
     assert n_frames == len(paths)
     return _write(dataset, outputs_dir, seq_dir, log, paths)
 
@@ -125,19 +131,24 @@ def submit_streams(streams: Optional[int] = None) -> int:
     return n
 
 
-def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: str, log) -> List[str]:
+def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: str, log, writer=None) -> List[str]:
     """``submit_sequence`` for many sequences at once: ``tracker`` (an inference_multi.MultiSequenceTracker) runs them
     in lockstep through ``track_many_logged``, ``log`` (a results.BankResultLog) holds the rows of all of them, and the
-    files are written when the last one ends.  Returns the files' paths, in the order of ``seq_dirs``."""
+    files are written when the last one ends.  ``writer``: a render.MultiAnnotatedWriter that is also given the
+    annotated frames (``track_many_annotated_logged``).  Returns the files' paths, in the order of ``seq_dirs``."""
     paths = [sequence_frames(dataset, d) for d in seq_dirs]
     log.reset()
-    counts = tracker.track_many_logged([_source(p) for p in paths], log)
+    if writer is None:
+        counts = tracker.track_many_logged([_source(p) for p in paths], log)
+    else:
+        counts = tracker.track_many_annotated_logged([_source(p) for p in paths], writer, log)
     assert counts == [len(p) for p in paths]
     return [_write(dataset, outputs_dir, d, log.sequence(i), paths[i]) for i, d in enumerate(seq_dirs)]
 
 
 def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
-           tracker_options: Optional[dict] = None, streams: Optional[int] = None) -> List[str]:
+           tracker_options: Optional[dict] = None, streams: Optional[int] = None,
+           annotate_dir: Optional[str] = None, annotate_options: Optional[dict] = None) -> List[str]:
     """submit_engine.py:187-252.  ``config``: SUBMIT_DIR, SUBMIT_MODEL, SUBMIT_DATA_SPLIT, DATA_ROOT and the inference
     thresholds (DET_SCORE_THRESH, TRACK_SCORE_THRESH, RESULT_SCORE_THRESH, MISS_TOLERANCE, USE_MOTION and the MOTION_*
     keys).  ``train_config`` (DATASET, USE_DAB and the model's keys) defaults to ``<SUBMIT_DIR>/train/config.yaml``;
@@ -145,9 +156,18 @@ def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
     ``SequenceTracker`` arguments (``raw_size``, ``area_thresh``) for every sequence's tracker.  Returns the files this
     rank wrote, in sequence order.  ``streams`` (default: MEMOTR_SUBMIT_STREAMS, else 1): above 1, that many of the
     rank's sequences are tracked side by side (inference_multi.py) and the files are written from one
-    ``BankResultLog``; the rows are those of ``streams=1`` up to float rounding."""
+    ``BankResultLog``; the rows are those of ``streams=1`` up to float rounding.  ``annotate_dir``: every frame is
+    also written with its reported tracks drawn in, as ``<annotate_dir>/<seq>/<frame index, 8 digits>.jpg``, from the
+    device (render.MultiAnnotatedWriter: no result is brought to the host for it); ``annotate_options``: ``quality``,
+    ``subsampling``, ``thickness``, ``font_scale``, ``fill_alpha`` of that writer.  The result files are the same with
+    and without it."""
     from .inference import SequenceTracker
     streams = submit_streams(streams)
+    unknown = set(annotate_options or {}) - {"quality", "subsampling", "thickness", "font_scale", "fill_alpha"}
+    if unknown:
+        raise TypeError(f"unknown annotate options {sorted(unknown)}")
+    if annotate_options and annotate_dir is None:
+        raise ValueError("annotate_options without annotate_dir")
     for key in ("SUBMIT_DIR", "SUBMIT_DATA_SPLIT", "DATA_ROOT"):
         if config.get(key) is None:
             raise ValueError(f"{key} must not be None for the submit process")
@@ -171,16 +191,32 @@ def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
         options["side_stream"] = torch.cuda.Stream(device)
     options.update(tracker_options or {})
     directory = split_dir(config["DATA_ROOT"], dataset, split)
-    if streams > 1:
-        from .inference_multi import MultiSequenceTracker
-        from .results import BankResultLog
-        for key in ("motion_lambda", "motion_min_length", "motion_max_length"):
-            options.pop(key)
-        tracker = MultiSequenceTracker(model, n_streams=streams, **options)
-        return submit_sequences(tracker, dataset, [os.path.join(directory, seq) for seq in
-                                                   sequence_names(directory, *_rank_and_world())],
-                                outputs_dir, BankResultLog(device))
-    log = ResultLog(device)
-    return [submit_sequence(lambda: SequenceTracker(model, **options), dataset,
-                            os.path.join(directory, seq), outputs_dir, log)
-            for seq in sequence_names(directory, *_rank_and_world())]
+    names = sequence_names(directory, *_rank_and_world())
+    writer = None
+    if annotate_dir is not None:
+        from .render import MultiAnnotatedWriter
+        writer = MultiAnnotatedWriter(annotate_dir, names=names, **(annotate_options or {}))
+    try:
+        if streams > 1:
+            from .inference_multi import MultiSequenceTracker
+            from .results import BankResultLog
+            for key in ("motion_lambda", "motion_min_length", "motion_max_length"):
+                options.pop(key)
+            tracker = MultiSequenceTracker(model, n_streams=streams, **options)
+            files = submit_sequences(tracker, dataset, [os.path.join(directory, seq) for seq in names], outputs_dir,
+                                     BankResultLog(device), writer)
+        else:
+            log = ResultLog(device)
+            files = [submit_sequence(lambda: SequenceTracker(model, **options), dataset, os.path.join(directory, seq),
+                                     outputs_dir, log, None if writer is None else (writer, i))
+                     for i, seq in enumerate(names)]
+    except BaseException:
+        if writer is not None:          # an error is already on its way: drain, but do not replace it
+            try:
+                writer.close()
+            except Exception:
+                pass
+        raise
+    if writer is not None:
+        writer.close()
+    return files
