@@ -419,6 +419,49 @@ int clipops_draw_table_f32(const float *boxes, const float *scores, const int64_
                            const float *ori_wh, float score_thresh, float area_thresh, int bgr, int font_scale,
                            int32_t *table, void *stream);
 
+/* ---- gap filling and short-track removal on a result table, where the rows live ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the bank entries: no entry point changed.)
+ * The offline pass over the rows of finished sequences that memotr_amd/postprocess.py states on the host (fill_gaps):
+ * a track that was not reported for 1 .. max_gap frames and came back under its id gets the missing rows by linear
+ * interpolation between the two rows around the hole, and a track with fewer than min_length rows is removed whole
+ * (and fills nothing).  Input: a table as clipops_result_rows_f32 (W = 3: frame, id, label) or
+ * clipops_bank_result_rows_f32 (W = 4: sequence, frame, id, label) leaves it -- rows_f (>= n, 5), rows_i (>= n, W), and
+ * its device counters: the rows read are the first min(counters[0], n), so the host passes a bound it knows (the rows
+ * offered) and the stored count never leaves the device.  Rows address a cell table [n_seq][n_ids][n_frames]; with
+ * W = 3 every row is of sequence 0 and n_seq is 1.
+ *   new row   for two rows of an id at frames f0 < f1 without a row between them and m = f1 - f0 - 1, 1 <= m <= max_gap:
+ *             frame f0 + k for k = 1 .. m, the id and the label of the row at f0, and each of x1, y1, x2, y2, score as
+ *             a + (b - a) * t,  t = float(k) / float(m + 1),  a and b the values at f0 and f1: a quotient, a difference,
+ *             a product and a sum in float32, each rounded once, never fused.
+ *   output    the rows of the surviving tracks bit-unchanged and the new rows, sorted by (sequence, frame, id), written
+ *             behind row out_counters[0] as it was when the call began, by clipops_result_rows_f32's capacity rule:
+ *             out_counters[0] grows by the rows stored, a row that would land at or past `capacity` is counted in
+ *             out_counters[1], and nothing is written past out_f (capacity, 5) / out_i (capacity, W).
+ *   status    a sticky word, OR-ed with CLIPOPS_FG_DUPLICATE when two rows share (sequence, frame, id), with
+ *             CLIPOPS_FG_ID / _FRAME / _SEQUENCE when a row's id, frame or sequence lies outside 0 .. n_ids - 1,
+ *             0 .. n_frames - 1, 0 .. n_seq - 1.  Such a row addresses no cell and is left out; of two rows in one
+ *             cell one is left out.  The caller zeroes the word and must not use the output when it is not 0.
+ *   workspace clipops_fill_gaps_workspace(n_seq, n_ids, n_frames) int32 words: two tables of n_seq * n_ids * n_frames
+ *             cells and n_seq * n_frames offsets; -1 for a negative size, -2 when the cells exceed 2^31 - 1.  No device
+ *             is touched.  Contents need no preparation and mean nothing afterwards.
+ * Five launches on `stream`, nothing synchronises: clear the cells; each row writes its index into its cell (integer
+ * compare-and-swap: the second writer sets the status bit); one workgroup per track finds, for every empty cell, the
+ * nearest occupied frame on either side -- a suffix minimum and a prefix maximum by wavefront shuffles, chunks of 1024
+ * frames carried through LDS -- counts the track's rows, marks the cells to fill or empties a short track; per
+ * (sequence, frame) the surviving cells are counted and the counts scanned; one workgroup per (sequence, frame) ranks
+ * its ids by ballots and writes the rows.  No float atomics: a table without duplicates gives the same bits every time.
+ * n == 0 launches nothing.  Arguments are checked on the host without touching a device: returns 1 for a negative size,
+ * max_gap or min_length, W not 3 or 4, W = 3 with n_seq > 1, or a null pointer with n > 0; 2 when the cells exceed
+ * 2^31 - 1; 3 when a launch failed. */
+#define CLIPOPS_FG_DUPLICATE 1
+#define CLIPOPS_FG_ID 2
+#define CLIPOPS_FG_FRAME 4
+#define CLIPOPS_FG_SEQUENCE 8
+long clipops_fill_gaps_workspace(int n_seq, int n_ids, int n_frames);
+int clipops_fill_gaps_f32(const float *rows_f, const int64_t *rows_i, const int32_t *counters, int n, int W, int n_seq,
+                          int n_ids, int n_frames, int max_gap, int min_length, int32_t *workspace, float *out_f,
+                          int64_t *out_i, int32_t *out_counters, int32_t *status, int capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

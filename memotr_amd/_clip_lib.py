@@ -67,7 +67,12 @@ SYMBOLS = {
                                      [c_void_p] * 3 + [c_int, c_void_p], c_int),
     "clipops_draw_table_f32": ([c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_float, c_float, c_int, c_int, c_void_p,
                                                                  c_void_p], c_int),
+    "clipops_fill_gaps_workspace": ([c_int] * 3, c_long),
+    "clipops_fill_gaps_f32": ([c_void_p] * 3 + [c_int] * 7 + [c_void_p] * 5 + [c_int, c_void_p], c_int),
 }
+
+# status bits of clipops_fill_gaps_f32 (CLIPOPS_FG_* in include/clip_ops_hip.h)
+FG_DUPLICATE, FG_ID, FG_FRAME, FG_SEQUENCE = 1, 2, 4, 8
 
 # clipops_handover_sources / clipops_handover_grads (include/clip_ops_hip.h); the index of a source is its position here
 HANDOVER_SOURCES = ("logits", "boxes", "outputs", "queries", "last_ref", "init_ref", "det_embed", "prev_ref",

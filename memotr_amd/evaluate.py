@@ -53,7 +53,8 @@ def _score(config: dict, dataset: str, split: str, tracker_dir: str, device) -> 
 
 
 def eval_model(config: dict, checkpoint: str, *, model=None, train_config: Optional[dict] = None,
-               tracker_options: Optional[dict] = None, streams: Optional[int] = None) -> Optional[dict]:
+               tracker_options: Optional[dict] = None, streams: Optional[int] = None,
+               postprocess: Optional[dict] = None) -> Optional[dict]:
     """Track ``EVAL_DATA_SPLIT`` with ``<EVAL_DIR>/<checkpoint>`` and score the result (eval_engine.py:66-124).
     ``train_config`` defaults to ``<EVAL_DIR>/train/config.yaml``; a ``model`` that is given receives the checkpoint's
     weights.  DanceTrack, SportsMOT and MOT17: ground truth under ``split_dir``, sequence names in
@@ -61,7 +62,8 @@ def eval_model(config: dict, checkpoint: str, *, model=None, train_config: Optio
     ``evaluation.summary`` of all sequences.  BDD100K: scored
     against ``EVAL_GT_DIR`` (a folder of ``<seq>.json``) and ``NotImplementedError`` without it, as in the reference;
     returns ``bdd_summary``.  With ``torch.distributed`` initialised every rank tracks its share, all meet at a barrier,
-    rank 0 scores and the others return None."""
+    rank 0 scores and the others return None.  ``streams`` and ``postprocess`` are ``submit``'s: the files that are
+    scored are written from the filled log when the pass is on."""
     if train_config is None:
         from .configs import load_yaml
         train_config = load_yaml(os.path.join(config["EVAL_DIR"], "train", "config.yaml"))
@@ -78,10 +80,12 @@ def eval_model(config: dict, checkpoint: str, *, model=None, train_config: Optio
     else:
         from .models.utils import get_model
         get_model(model).load_state_dict(torch.load(path, map_location="cpu")["model"])
-    # (``streams``: submit's; handed on only when given, None leaves MEMOTR_SUBMIT_STREAMS / 1 to submit)
+    # (``streams`` and ``postprocess``: submit's; handed on only when given, None leaves MEMOTR_SUBMIT_STREAMS / 1 and
+    # MEMOTR_POSTPROCESS / off to submit)
     submit(dict(config, SUBMIT_DIR=config["EVAL_DIR"], SUBMIT_MODEL=checkpoint, SUBMIT_DATA_SPLIT=split), model=model,
            train_config=dict(train_config, DATASET=dataset), tracker_options=tracker_options,
-           **({} if streams is None else {"streams": streams}))
+           **({} if streams is None else {"streams": streams}),
+           **({} if postprocess is None else {"postprocess": postprocess}))
     _barrier()                                      # every rank's files are in tracker/
     metrics = None
     if _rank_and_world()[0] == 0:
@@ -97,7 +101,7 @@ def eval_model(config: dict, checkpoint: str, *, model=None, train_config: Optio
 
 def evaluate(config: dict, on_metrics: Optional[Callable[[int, dict], None]] = None, *, model=None,
              train_config: Optional[dict] = None, tracker_options: Optional[dict] = None,
-             streams: Optional[int] = None):
+             streams: Optional[int] = None, postprocess: Optional[dict] = None):
     """eval_engine.py:12-63.  ``EVAL_MODE`` "specific": ``eval_model`` of ``EVAL_MODEL``, returns its metrics.
     "continue": every ``checkpoint_{i}.pth`` of ``EVAL_DIR`` from ``eval_states.yaml``'s ``NEXT_INDEX`` on; an index
     whose ``pedestrian_summary.txt`` exists is not evaluated again; ``eval_states.yaml`` is rewritten after each index,
@@ -106,7 +110,8 @@ def evaluate(config: dict, on_metrics: Optional[Callable[[int, dict], None]] = N
     split, eval_dir = config["EVAL_DATA_SPLIT"], config["EVAL_DIR"]
     outputs_dir = os.path.join(eval_dir, split)
     main = _rank_and_world()[0] == 0
-    kwargs = dict(model=model, train_config=train_config, tracker_options=tracker_options, streams=streams)
+    kwargs = dict(model=model, train_config=train_config, tracker_options=tracker_options, streams=streams,
+                  postprocess=postprocess)
 
     def record(index, checkpoint, metrics):
         if not main:

@@ -13,6 +13,9 @@ the tables, their growth, ``reset`` and the packed, validated read are ``_RowTab
     log.reset()                                   # next sequence
 
 On CPU tensors ``append`` runs ``host_rows``, the torch statement the kernel is held to (tests/test_result_log_gpu.py).
+
+``filled`` of either log gives a new log with the offline pass of postprocess.py applied (short tracks removed, holes
+of a few frames interpolated), made on the device from the tables as they stand; the writers are the same.
 """
 from __future__ import annotations
 
@@ -54,6 +57,16 @@ def host_rows(boxes: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor, labe
     return rows_f, rows_i
 
 
+def _raise_for_status(status: int) -> None:
+    """The status word of ``clipops_fill_gaps_f32`` (CLIPOPS_FG_* in include/clip_ops_hip.h) as an error."""
+    if status == 0:
+        return
+    said = [text for bit, text in ((1, "a duplicate (frame, id)"), (2, "an id out of range (outside 0 .. n_ids - 1)"),
+                                   (4, "a frame out of range (outside 0 .. n_frames - 1)"),
+                                   (8, "a sequence out of range (outside 0 .. n_sequences - 1)")) if status & bit]
+    raise RuntimeError("result log: the rows cannot be filled: " + "; ".join(said or [f"status {status}"]))
+
+
 class _RowTable:
     """``rows_f`` (capacity, 5) float32, ``rows_i`` (capacity, ``WIDTH_I``) int64 and ``counters`` (2,) int32 (rows
     stored, rows dropped for lack of room) on ``device``, the bound on the rows in use and the last read.  A log adds
@@ -69,6 +82,7 @@ class _RowTable:
         self.counters = torch.zeros((2,), dtype=torch.int32, device=self.device)
         self._bound = 0           # the rows appended can be no more than the rows offered: known without a read
         self._rows = None         # the last read, until the next append / reset
+        self.status = None        # of a log made by ``filled`` on the device: (1,) int32, what the kernels objected to
 
     def _make_room(self, offered: int) -> None:
         """Before an append of at most ``offered`` rows (the caller then adds them to ``_bound``)."""
@@ -92,7 +106,7 @@ class _RowTable:
     def reset(self) -> None:
         """Empty the log for the next sequence (stream-ordered; the tables keep their size)."""
         self.counters.zero_()
-        self._bound, self._rows = 0, None
+        self._bound, self._rows, self.status = 0, None, None
 
     def read(self):
         """The rows on the host (``_as_rows`` of the stored part of the tables): one packed copy through a pinned buffer
@@ -100,6 +114,12 @@ class _RowTable:
         if self._rows is not None:
             return self._rows
         b, w = self._bound, self.WIDTH_I
+        if self.status is not None and b > 0:
+            # a filled log: its bound is the room it was given, far above the rows stored, so the counters and the
+            # status word come first (a second small read) and the copy below takes the stored rows only
+            head = to_host(torch.cat((self.counters, self.status))).numpy()
+            _raise_for_status(int(head[2]))
+            b = self._bound = min(b, max(int(head[0]), 0))
         if self.device.type == "cuda":
             raw = to_host(torch.cat((self.counters.view(torch.uint8), self.rows_i[:b].reshape(-1).view(torch.uint8),
                                      self.rows_f[:b].reshape(-1).view(torch.uint8)))).numpy()
@@ -115,6 +135,69 @@ class _RowTable:
             raise RuntimeError(f"result log: {stored} rows stored, {b} offered (counters written from elsewhere?)")
         self._rows = self._as_rows(rows_i[:stored], rows_f[:stored])
         return self._rows
+
+    def _like(self, capacity: int):
+        """An empty log of this class on this device."""
+        return type(self)(self.device, capacity)
+
+    def _extent(self):
+        """``(n_sequences, n_frames, n_ids)`` of the stored rows -- the largest of each column plus one, 0 without a
+        row: one small read (three numbers; the stored count stays on the device)."""
+        w = self.WIDTH_I
+        if self._bound == 0:
+            return 0, 0, 0
+        stored = self.counters[0].clamp(0, self._bound)
+        valid = torch.arange(self._bound, device=self.device) < stored
+        top = to_host(torch.where(valid[:, None], self.rows_i[:self._bound], -1).amax(dim=0)).tolist()
+        return (int(top[0]) + 1 if w == BANK_ROW_I else 1), int(top[w - 3]) + 1, int(top[w - 2]) + 1
+
+    def _filled(self, max_gap: int, min_length: int, n_seq, n_frames, n_ids):
+        """``filled`` of both logs on a CUDA device: ``clipops_fill_gaps_f32`` (include/clip_ops_hip.h) from these
+        tables into those of a new log.  The new log's room is what the pass can give at most -- every cell of the
+        ``n_seq * n_ids * n_frames`` table, or every offered row with ``max_gap`` new ones behind it."""
+        from . import _clip_lib as L      # no substitute: a missing library is an error
+        max_gap, min_length = int(max_gap), int(min_length)
+        if max_gap < 0 or min_length < 0:
+            raise ValueError(f"max_gap and min_length must not be negative, not {max_gap} and {min_length}")
+        if self._bound == 0:
+            return self._like(1)
+        if n_seq is None or n_frames is None or n_ids is None:
+            seen = self._extent()
+            n_seq, n_frames, n_ids = (s if given is None else int(given) for s, given in zip(seen, (n_seq, n_frames, n_ids)))
+        n_seq, n_frames, n_ids = int(n_seq), int(n_frames), int(n_ids)
+        if min(n_seq, n_frames, n_ids) < 0:
+            raise ValueError(f"negative table size: {n_seq} sequences, {n_frames} frames, {n_ids} ids")
+        words = L.lib.clipops_fill_gaps_workspace(n_seq, n_ids, n_frames)
+        if words < 0:
+            raise ValueError(f"result log: {n_seq} sequences x {n_ids} ids x {n_frames} frames are more than 2^31 - 1 cells")
+        new = self._like(max(1, min(n_seq * n_ids * n_frames, self._bound * (1 + max_gap))))
+        new.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        workspace = torch.empty((max(1, words),), dtype=torch.int32, device=self.device)
+        L.check(L.lib.clipops_fill_gaps_f32(
+            self.rows_f.data_ptr(), self.rows_i.data_ptr(), self.counters.data_ptr(), self._bound, self.WIDTH_I, n_seq,
+            n_ids, n_frames, max_gap, min_length, workspace.data_ptr(), new.rows_f.data_ptr(), new.rows_i.data_ptr(),
+            new.counters.data_ptr(), new.status.data_ptr(), new.capacity,
+            torch.cuda.current_stream(self.device).cuda_stream), "clipops_fill_gaps_f32")
+        new._bound = new.capacity
+        return new
+
+    def _store(self, rows_i: np.ndarray, rows_f: np.ndarray) -> None:
+        """Host rows into the tables of this (CPU, empty) log."""
+        m = rows_i.shape[0]
+        self._make_room(m)
+        self.rows_i[:m], self.rows_f[:m] = torch.from_numpy(rows_i), torch.from_numpy(rows_f)
+        self.counters[0] = m
+        self._bound = m
+
+
+def _check_extent(rows: Rows, n_frames, n_ids) -> None:
+    """What the kernels' status word says of rows outside the table a caller named, for a CPU log."""
+    status = 0
+    if n_ids is not None and len(rows.ids) and (rows.ids.min() < 0 or rows.ids.max() >= int(n_ids)):
+        status |= 2
+    if n_frames is not None and len(rows.frames) and (rows.frames.min() < 0 or rows.frames.max() >= int(n_frames)):
+        status |= 4
+    _raise_for_status(status)
 
 
 class _SequenceRows:
@@ -214,6 +297,26 @@ class ResultLog(_RowTable, _SequenceRows):
         return Rows(rows_i[:, 0].copy(), rows_i[:, 1].copy(), rows_i[:, 2].copy(),
                     np.ascontiguousarray(rows_f[:, :4]), rows_f[:, 4].copy())
 
+    @torch.no_grad()
+    def filled(self, max_gap: int, min_length: int = 0, n_frames: int = None, n_ids: int = None) -> "ResultLog":
+        """A new log on the same device with the offline pass of postprocess.py applied: tracks of fewer than
+        ``min_length`` rows removed, holes of at most ``max_gap`` frames filled by linear interpolation, rows sorted by
+        (frame, id).  This log stays as it is.  For a finished sequence: nothing here is called per frame.  On a CUDA
+        device the rows never leave it (``clipops_fill_gaps_f32``); ``n_frames`` and ``n_ids`` size its cell table --
+        every frame is below ``n_frames`` and every id below ``n_ids`` (``track_logged``'s return value and
+        ``tracker.tracker.max_obj_id``).  Where both are passed nothing is read back; otherwise one small read finds
+        them.  What the kernels object to (a duplicate (frame, id), an id or a frame out of range) is raised by the new
+        log's ``read()``.  A CPU log runs the host statement, ``postprocess.fill_gaps``, at once."""
+        if self.device.type == "cuda":
+            return self._filled(max_gap, min_length, 1, n_frames, n_ids)
+        from .postprocess import fill_gaps
+        rows = self.read()
+        _check_extent(rows, n_frames, n_ids)
+        r = fill_gaps(rows, max_gap, min_length)
+        new = self._like(max(1, len(r.frames)))
+        new._store(np.stack((r.frames, r.ids, r.labels), axis=1), np.concatenate((r.boxes_xyxy, r.scores[:, None]), axis=1))
+        return new
+
 
 class BankResultLog(_RowTable):
     """The table of sequences tracked side by side (inference_multi.MultiSequenceTracker): one table for all of
@@ -252,6 +355,32 @@ class BankResultLog(_RowTable):
             out[int(seq)] = Rows(rows_i[pick, 1].copy(), rows_i[pick, 2].copy(), rows_i[pick, 3].copy(),
                                  np.ascontiguousarray(rows_f[pick, :4]), rows_f[pick, 4].copy())
         return out
+
+    def _like(self, capacity: int):
+        return type(self)(self.device, capacity, self.dataset_name)
+
+    @torch.no_grad()
+    def filled(self, max_gap: int, min_length: int = 0, n_frames: int = None, n_ids: int = None,
+               n_sequences: int = None) -> "BankResultLog":
+        """``ResultLog.filled`` for every sequence of the table at once, each sequence on its own: a new log whose
+        ``read()`` gives ``postprocess.fill_gaps`` of every sequence's ``Rows`` (a sequence that loses all its tracks
+        has no entry).  ``n_frames``: above every frame of every sequence; ``n_ids``: above every id;
+        ``n_sequences``: above every sequence number.  Where all three are passed nothing is read back."""
+        if self.device.type == "cuda":
+            return self._filled(max_gap, min_length, n_sequences, n_frames, n_ids)
+        from .postprocess import fill_gaps
+        parts_i, parts_f = [np.zeros((0, BANK_ROW_I), np.int64)], [np.zeros((0, ROW_F), np.float32)]
+        for seq, rows in sorted(self.read().items()):
+            if n_sequences is not None and not 0 <= seq < int(n_sequences):
+                _raise_for_status(8)
+            _check_extent(rows, n_frames, n_ids)
+            r = fill_gaps(rows, max_gap, min_length)
+            parts_i.append(np.stack((np.full_like(r.frames, seq), r.frames, r.ids, r.labels), axis=1))
+            parts_f.append(np.concatenate((r.boxes_xyxy, r.scores[:, None]), axis=1))
+        rows_i, rows_f = np.concatenate(parts_i), np.concatenate(parts_f)
+        new = self._like(max(1, rows_i.shape[0]))
+        new._store(rows_i, rows_f)
+        return new
 
     def sequence(self, seq: int) -> _SequenceRows:
         """The rows of sequence ``seq`` behind ``ResultLog``'s writers (a sequence without a row: an empty log)."""

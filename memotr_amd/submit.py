@@ -91,11 +91,12 @@ def _write(dataset: str, outputs_dir: str, seq_dir: str, rows, paths) -> str:
 
 
 def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outputs_dir: str, log: ResultLog,
-                    annotate=None) -> str:
+                    annotate=None, postprocess: Optional[dict] = None) -> str:
     """Track the sequence in ``seq_dir`` with a fresh tracker from ``tracker_factory()`` and write its result file
     (``_write``).  ``log`` is emptied first and holds the sequence's rows afterwards.  ``annotate``: ``(writer, i)`` --
     a render.MultiAnnotatedWriter that is also given the annotated frames, as those of its sequence ``i``
-    (``track_annotated_logged``).  Returns the file's path."""
+    (``track_annotated_logged``).  ``postprocess``: ``dict(max_gap=..., min_length=...)`` -- the file is written from
+    ``log.filled(...)`` (results.py), ``log`` itself keeps the rows as tracked.  Returns the file's path."""
     paths = sequence_frames(dataset, seq_dir)
     tracker = tracker_factory()
     log.reset()
@@ -104,7 +105,10 @@ def submit_sequence(tracker_factory: Callable, dataset: str, seq_dir: str, outpu
     else:
         n_frames = tracker.track_annotated_logged(_source(paths), annotate[0], log, sequence=annotate[1])
     assert n_frames == len(paths)
-    return _write(dataset, outputs_dir, seq_dir, log, paths)
+    rows = log
+    if postprocess is not None:         # the host knows both sizes of the cell table: nothing is read for them
+        rows = log.filled(n_frames=n_frames, n_ids=tracker.tracker.max_obj_id, **postprocess)
+    return _write(dataset, outputs_dir, seq_dir, rows, paths)
 
 
 def load_model(train_config: dict, checkpoint: str):
@@ -131,11 +135,14 @@ def submit_streams(streams: Optional[int] = None) -> int:
     return n
 
 
-def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: str, log, writer=None) -> List[str]:
+def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: str, log, writer=None,
+                     postprocess: Optional[dict] = None) -> List[str]:
     """``submit_sequence`` for many sequences at once: ``tracker`` (an inference_multi.MultiSequenceTracker) runs them
     in lockstep through ``track_many_logged``, ``log`` (a results.BankResultLog) holds the rows of all of them, and the
     files are written when the last one ends.  ``writer``: a render.MultiAnnotatedWriter that is also given the
-    annotated frames (``track_many_annotated_logged``).  Returns the files' paths, in the order of ``seq_dirs``."""
+    annotated frames (``track_many_annotated_logged``).  ``postprocess``: as for ``submit_sequence``, one
+    ``log.filled(...)`` over all sequences (the ids live on the device: one small read finds the largest).  Returns the
+    files' paths, in the order of ``seq_dirs``."""
     paths = [sequence_frames(dataset, d) for d in seq_dirs]
     log.reset()
     if writer is None:
@@ -143,12 +150,15 @@ def submit_sequences(tracker, dataset: str, seq_dirs: List[str], outputs_dir: st
     else:
         counts = tracker.track_many_annotated_logged([_source(p) for p in paths], writer, log)
     assert counts == [len(p) for p in paths]
+    if postprocess is not None:
+        log = log.filled(n_frames=max(counts, default=0), n_sequences=len(seq_dirs), **postprocess)
     return [_write(dataset, outputs_dir, d, log.sequence(i), paths[i]) for i, d in enumerate(seq_dirs)]
 
 
 def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
            tracker_options: Optional[dict] = None, streams: Optional[int] = None,
-           annotate_dir: Optional[str] = None, annotate_options: Optional[dict] = None) -> List[str]:
+           annotate_dir: Optional[str] = None, annotate_options: Optional[dict] = None,
+           postprocess: Optional[dict] = None) -> List[str]:
     """submit_engine.py:187-252.  ``config``: SUBMIT_DIR, SUBMIT_MODEL, SUBMIT_DATA_SPLIT, DATA_ROOT and the inference
     thresholds (DET_SCORE_THRESH, TRACK_SCORE_THRESH, RESULT_SCORE_THRESH, MISS_TOLERANCE, USE_MOTION and the MOTION_*
     keys).  ``train_config`` (DATASET, USE_DAB and the model's keys) defaults to ``<SUBMIT_DIR>/train/config.yaml``;
@@ -160,9 +170,15 @@ def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
     also written with its reported tracks drawn in, as ``<annotate_dir>/<seq>/<frame index, 8 digits>.jpg``, from the
     device (render.MultiAnnotatedWriter: no result is brought to the host for it); ``annotate_options``: ``quality``,
     ``subsampling``, ``thickness``, ``font_scale``, ``fill_alpha`` of that writer.  The result files are the same with
-    and without it."""
+    and without it.  ``postprocess`` (default: MEMOTR_POSTPROCESS="max_gap=20,min_length=5", else off):
+    ``dict(max_gap=..., min_length=...)`` -- every file is written from the filled log (postprocess.py: tracks of fewer
+    than ``min_length`` rows removed, holes of at most ``max_gap`` frames interpolated), made on the device when the
+    sequence ends; unknown keys are a ``TypeError``.  Annotated frames are drawn online, frame by frame, and are not
+    affected: they show the tracks as reported, holes included."""
     from .inference import SequenceTracker
+    from .postprocess import postprocess_options
     streams = submit_streams(streams)
+    postprocess = postprocess_options(postprocess)
     unknown = set(annotate_options or {}) - {"quality", "subsampling", "thickness", "font_scale", "fill_alpha"}
     if unknown:
         raise TypeError(f"unknown annotate options {sorted(unknown)}")
@@ -204,11 +220,11 @@ def submit(config: dict, *, model=None, train_config: Optional[dict] = None,
                 options.pop(key)
             tracker = MultiSequenceTracker(model, n_streams=streams, **options)
             files = submit_sequences(tracker, dataset, [os.path.join(directory, seq) for seq in names], outputs_dir,
-                                     BankResultLog(device), writer)
+                                     BankResultLog(device), writer, postprocess)
         else:
             log = ResultLog(device)
             files = [submit_sequence(lambda: SequenceTracker(model, **options), dataset, os.path.join(directory, seq),
-                                     outputs_dir, log, None if writer is None else (writer, i))
+                                     outputs_dir, log, None if writer is None else (writer, i), postprocess)
                      for i, seq in enumerate(names)]
     except BaseException:
         if writer is not None:          # an error is already on its way: drain, but do not replace it
