@@ -1,0 +1,470 @@
+// clip_tracks.h -- the device side of the online tracker and of the submit path: result rows, the track bank, the
+// bank's result rows and the overlay's draw table.  One statement of the kept-track rule and of the counters' capacity
+// rule serves all of them (and clip_fill_gaps.h, included after this header).
+// Included by clip_ops.hip after clip_common.h.
+#pragma once
+
+namespace {
+// The kept-track rule (SequenceTracker._report): a track is reported when its best class score and its pixel area pass
+// the thresholds; its box goes out as pixel xyxy.  Every float operation rounds once.
+struct KeptTrack {
+    bool keep;
+    float score, x1, y1, x2, y2;                    // the box only where `keep`
+};
+
+__device__ __forceinline__ KeptTrack kept_track(const float *__restrict__ boxes, const float *__restrict__ scores, long i,
+                                                int K, float ori_w, float ori_h, float score_thresh, float area_thresh) {
+    KeptTrack r = {false, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float *sc = scores + i * K;
+    float s = sc[0];
+    for (int k = 1; k < K; ++k) {                   // torch's max: a NaN wins and stays
+        const float v = sc[k];
+        if (v > s || v != v) s = v;
+    }
+    const float cx = boxes[4 * i], cy = boxes[4 * i + 1], w = boxes[4 * i + 2], h = boxes[4 * i + 3];
+    const float area = __fmul_rn(__fmul_rn(__fmul_rn(w, ori_w), h), ori_h);
+    r.score = s;
+    if (!(s > score_thresh && area > area_thresh)) return r;      // false for a NaN on either side
+    const float hw = __fmul_rn(0.5f, w), hh = __fmul_rn(0.5f, h);
+    r.keep = true;
+    r.x1 = __fmul_rn(__fsub_rn(cx, hw), ori_w);
+    r.y1 = __fmul_rn(__fsub_rn(cy, hh), ori_h);
+    r.x2 = __fmul_rn(__fadd_rn(cx, hw), ori_w);
+    r.y2 = __fmul_rn(__fadd_rn(cy, hh), ori_h);
+    return r;
+}
+
+// the five float columns of a result row
+__device__ __forceinline__ void kept_store(float *__restrict__ rf, const KeptTrack &t) {
+    rf[0] = t.x1, rf[1] = t.y1, rf[2] = t.x2, rf[3] = t.y2, rf[4] = t.score;
+}
+
+// The capacity rule of a result table's counters: of `base` new rows the table stores what fits behind the stored0 it
+// holds and counts the rest as dropped.  One lane calls it, after every thread has read the counters.  I: the type the
+// caller counts its rows in (int; long in fg_scan_kernel, whose sums are clamped, not wrapped).
+template <typename I>
+__device__ __forceinline__ void store_counters(int32_t *__restrict__ counters, int stored0, int dropped0, I base,
+                                               int capacity) {
+    const I room = stored0 < 0 ? 0 : (capacity > stored0 ? capacity - stored0 : 0);
+    const I stored = base < room ? base : room;
+    counters[0] = (int)(stored0 + stored);
+    counters[1] = (int)(dropped0 + (base - stored));
+}
+
+// ---- result rows of the submit path (ABI 12): the score / area filter and the pixel boxes of SequenceTracker._report,
+//      compacted onto the end of a device-resident table -- one launch per frame, no host read ----
+// one workgroup; rows in chunks of 256: a 64-bit ballot and the population count of the lower lanes place a row inside
+// its wavefront, the four wave totals go through LDS, `base` runs across chunks.  Both counters are read before
+// anything is written and written once, by one lane, with plain stores.  Every float operation rounds once.
+__global__ __launch_bounds__(256) void result_rows_kernel(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                          const int64_t *__restrict__ ids,
+                                                          const int64_t *__restrict__ labels, int n, int K, int64_t frame,
+                                                          float ori_w, float ori_h, float score_thresh, float area_thresh,
+                                                          float *__restrict__ rows_f, int64_t *__restrict__ rows_i,
+                                                          int32_t *__restrict__ counters, int capacity) {
+    __shared__ int wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stored0 = counters[0], dropped0 = counters[1];
+    int base = 0;                                   // rows kept by the chunks before this one
+    for (int c0 = 0; c0 < n; c0 += 256) {           // (n is uniform: every thread makes every trip)
+        const int i = c0 + (int)threadIdx.x;
+        KeptTrack t = {false, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (i < n) t = kept_track(boxes, scores, i, K, ori_w, ori_h, score_thresh, area_thresh);
+        int before, total;
+        bank_ranks<4>(t.keep, lane, wave, wave_total, before, total);
+        if (t.keep) {
+            const long pos = (long)stored0 + base + before;
+            if (pos >= 0 && pos < capacity) {
+                kept_store(rows_f + pos * 5, t);
+                int64_t *ri = rows_i + pos * 3;
+                ri[0] = frame;
+                ri[1] = ids[i];
+                ri[2] = labels[i];
+            }
+        }
+        base += total;
+        __syncthreads();                            // wave_total is written again by the next chunk
+    }
+    if (threadIdx.x == 0) store_counters(counters, stored0, dropped0, base, capacity);
+}
+
+// ---- track bank (include/clip_ops_hip.h: clipops_bank_*): the online tracker's bookkeeping for B sequences at once,
+//      on fixed-size slot tables -- no row count ever reaches the host ----
+// One workgroup per stream, three phases separated by barriers:
+//   1. the slots that are free when the call begins, in slot order, into the bank's free_list (ballot + population count
+//      inside a wavefront, wave totals through LDS, a running base across chunks of 1024 slots);
+//   2. one wavefront per live slot: refresh from model row n_det + s, age, retire (the row is zeroed);
+//   3. detect rows in chunks of 1024: one thread decides a row's birth and label, the same ballot scheme ranks the born
+//      rows, rank j takes free_list[j]; the (row, slot) pairs of the chunk go through LDS and one wavefront copies a pair.
+// Phases 2 and 3 write disjoint slots (live / free at the start).  Every counter is read before anything is written and
+// written once by one lane with plain stores; no atomics.
+// (16 wavefronts: phase 2 is a chain of dependent loads per slot, and a wavefront walks its slots one after another)
+constexpr int BANK_THREADS = 1024, BANK_WAVES = BANK_THREADS / 64;
+
+__global__ __launch_bounds__(BANK_THREADS) void bank_update_kernel(clipops_bank_model m, clipops_bank bank, int n_det, int cap,
+                                                          int K, int C, int use_dab, float det_thresh,
+                                                          float track_thresh, int64_t miss_tolerance) {
+#pragma clang fp contract(off)
+    __shared__ int wave_total[BANK_WAVES], wave_live[BANK_WAVES], pair_row[BANK_THREADS], pair_slot[BANK_THREADS];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int QW = use_dab ? C : 2 * C;
+    const long bc = (long)b * cap;
+    int64_t *ids = bank.ids + bc, *labels = bank.labels + bc, *dtime = bank.disappear_time + bc;
+    int32_t *free_list = bank.free_list + bc;
+    float *boxes = bank.boxes + bc * 4, *ref_pts = bank.ref_pts + bc * 4;
+    float *logits = bank.logits + bc * K, *scores = bank.scores + bc * K;
+    float *out_embed = bank.output_embed + bc * C, *long_mem = bank.long_memory + bc * C;
+    float *last_out = bank.last_output + bc * C, *query = bank.query_embed + bc * QW;
+    const float *m_logits = m.ptr[CLIPOPS_BK_LOGITS] + b * m.batch_stride[CLIPOPS_BK_LOGITS];
+    const float *m_boxes = m.ptr[CLIPOPS_BK_BOXES] + b * m.batch_stride[CLIPOPS_BK_BOXES];
+    const float *m_out = m.ptr[CLIPOPS_BK_OUTPUTS] + b * m.batch_stride[CLIPOPS_BK_OUTPUTS];
+    const float *m_ref = m.ptr[CLIPOPS_BK_LAST_REF] + b * m.batch_stride[CLIPOPS_BK_LAST_REF];
+    const float *m_query = m.ptr[CLIPOPS_BK_QUERIES] + b * m.batch_stride[CLIPOPS_BK_QUERIES];
+    const long rs_logits = m.row_stride[CLIPOPS_BK_LOGITS], rs_boxes = m.row_stride[CLIPOPS_BK_BOXES];
+    const long rs_out = m.row_stride[CLIPOPS_BK_OUTPUTS], rs_ref = m.row_stride[CLIPOPS_BK_LAST_REF];
+    const long rs_query = m.row_stride[CLIPOPS_BK_QUERIES];
+    const int64_t next0 = bank.next_id[b];
+    const int dropped0 = bank.counters[2 * b + 1];
+
+    // ---- 1. free slots, as they are before this call
+    int n_free = 0;
+    for (int s0 = 0; s0 < cap; s0 += BANK_THREADS) {
+        const int s = s0 + (int)threadIdx.x;
+        const bool is_free = s < cap && ids[s] < 0;
+        int before, total;
+        bank_ranks<BANK_WAVES>(is_free, lane, wave, wave_total, before, total);
+        if (is_free) free_list[n_free + before] = s;
+        n_free += total;
+        __syncthreads();                            // wave_total is written again; ids are written from here on
+    }
+
+    // ---- 2. live slots: one wavefront each (s, id, label and the decision are uniform over the wavefront)
+    int live = 0;
+    for (int s = wave; s < cap; s += BANK_WAVES) {
+        const int64_t id = ids[s], d0 = dtime[s];
+        int64_t lab = labels[s];
+        if (id < 0) continue;
+        const long r = (long)n_det + s;
+        const float *lg = m_logits + r * rs_logits;
+        lab = lab < 0 ? 0 : (lab >= K ? K - 1 : lab);
+        const float own = sigmoidf(lg[lab]);
+        const int64_t d = own < track_thresh ? d0 + 1 : 0;             // (a NaN score does not age the track)
+        if (d >= miss_tolerance) {                                      // retired: the slot holds zeros again
+            for (int c = lane; c < K; c += 64) logits[(long)s * K + c] = 0.f, scores[(long)s * K + c] = 0.f;
+            if (lane < 4) boxes[s * 4L + lane] = 0.f, ref_pts[s * 4L + lane] = 0.f;
+            for (int c = lane; c < C; c += 64)
+                out_embed[(long)s * C + c] = 0.f, long_mem[(long)s * C + c] = 0.f, last_out[(long)s * C + c] = 0.f;
+            for (int c = lane; c < QW; c += 64) query[(long)s * QW + c] = 0.f;
+            if (lane == 0) ids[s] = -1, labels[s] = 0, dtime[s] = 0;
+        } else {
+            for (int c = lane; c < K; c += 64) {
+                const float v = lg[c];
+                logits[(long)s * K + c] = v;
+                scores[(long)s * K + c] = sigmoidf(v);
+            }
+            if (lane < 4) boxes[s * 4L + lane] = m_boxes[r * rs_boxes + lane];
+            for (int c = lane; c < C; c += 64) out_embed[(long)s * C + c] = m_out[r * rs_out + c];
+            if (lane == 0) dtime[s] = d;
+            ++live;
+        }
+    }
+    if (lane == 0) wave_live[wave] = live;
+    __syncthreads();
+
+    // ---- 3. births
+    int born_base = 0;                              // born rows of the chunks before this one
+    for (int c0 = 0; c0 < n_det; c0 += BANK_THREADS) {      // (n_det is uniform: every thread makes every trip)
+        const int r = c0 + (int)threadIdx.x;
+        bool born = false;
+        int label = 0;
+        if (r < n_det) {
+            const float *lg = m_logits + r * rs_logits;
+            float best = sigmoidf(lg[0]);
+            bool nan = best != best;
+            for (int k = 1; k < K; ++k) {           // the lowest index of the maximum
+                const float v = sigmoidf(lg[k]);
+                nan |= v != v;
+                if (v > best) best = v, label = k;
+            }
+            born = !nan && best >= det_thresh;
+        }
+        int before, total;
+        bank_ranks<BANK_WAVES>(born, lane, wave, wave_total, before, total);
+        const int room = n_free > born_base ? n_free - born_base : 0;
+        const int n_pairs = total < room ? total : room;
+        if (born && before < n_pairs) {
+            const int slot = free_list[born_base + before];
+            pair_row[before] = r;
+            pair_slot[before] = slot;
+            ids[slot] = next0 + born_base + before;
+            labels[slot] = label;
+            dtime[slot] = 0;
+        }
+        __syncthreads();
+        for (int p = wave; p < n_pairs; p += BANK_WAVES) {
+            const long row = pair_row[p], s = pair_slot[p];
+            const float *lg = m_logits + row * rs_logits;
+            for (int c = lane; c < K; c += 64) {
+                const float v = lg[c];
+                logits[s * K + c] = v;
+                scores[s * K + c] = sigmoidf(v);
+            }
+            if (lane < 4) {
+                boxes[s * 4 + lane] = m_boxes[row * rs_boxes + lane];
+                ref_pts[s * 4 + lane] = m_ref[row * rs_ref + lane];
+            }
+            for (int c = lane; c < C; c += 64) {
+                const float o = m_out[row * rs_out + c], q = m_query[row * rs_query + c];
+                out_embed[s * C + c] = o;
+                last_out[s * C + c] = o;
+                long_mem[s * C + c] = q;
+                if (use_dab) {
+                    query[s * QW + c] = q;
+                } else {
+                    query[s * QW + c] = m.det_embed[row * m.det_row_stride + c];
+                    query[s * QW + C + c] = q;
+                }
+            }
+        }
+        born_base += total;
+        __syncthreads();                            // wave_total and the pairs are written again by the next chunk
+    }
+    if (threadIdx.x == 0) {
+        const int placed = born_base < n_free ? born_base : n_free;
+        bank.next_id[b] = next0 + placed;
+        int live_after = placed;
+        for (int v = 0; v < BANK_WAVES; ++v) live_after += wave_live[v];
+        bank.counters[2 * b] = live_after;
+        bank.counters[2 * b + 1] = dropped0 + (born_base - placed);
+    }
+}
+
+// clipops_result_rows_f32's filter and arithmetic over the B * cap slots of a bank, streams in order, free slots skipped:
+// one workgroup, so that the rows of all streams land in one table in a fixed order.
+__global__ __launch_bounds__(256) void bank_result_rows_kernel(const float *__restrict__ boxes,
+                                                               const float *__restrict__ scores,
+                                                               const int64_t *__restrict__ ids,
+                                                               const int64_t *__restrict__ labels, int n_slots, int cap,
+                                                               int K, const int64_t *__restrict__ seq_frame,
+                                                               const float *__restrict__ ori_wh, float score_thresh,
+                                                               float area_thresh, float *__restrict__ rows_f,
+                                                               int64_t *__restrict__ rows_i,
+                                                               int32_t *__restrict__ counters, int capacity) {
+    __shared__ int wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stored0 = counters[0], dropped0 = counters[1];
+    int base = 0;
+    for (int c0 = 0; c0 < n_slots; c0 += 256) {
+        const int i = c0 + (int)threadIdx.x;
+        KeptTrack t = {false, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int b = 0;
+        if (i < n_slots && ids[i] >= 0) {
+            b = i / cap;
+            t = kept_track(boxes, scores, i, K, ori_wh[2 * b], ori_wh[2 * b + 1], score_thresh, area_thresh);
+        }
+        int before, total;
+        bank_ranks<4>(t.keep, lane, wave, wave_total, before, total);
+        if (t.keep) {
+            const long pos = (long)stored0 + base + before;
+            if (pos >= 0 && pos < capacity) {
+                kept_store(rows_f + pos * 5, t);
+                int64_t *ri = rows_i + pos * 4;
+                ri[0] = seq_frame[2 * b];
+                ri[1] = seq_frame[2 * b + 1];
+                ri[2] = ids[i];
+                ri[3] = labels[i];
+            }
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) store_counters(counters, stored0, dropped0, base, capacity);
+}
+
+// ---- the overlay's draw table from device tracks (include/clip_ops_hip.h: clipops_draw_table_f32) ----
+// One workgroup per stream.  A slot's key is its id when the slot is kept (bank_result_rows_kernel's filter, id below
+// 2^31) and -1 otherwise; the row of a kept slot is the number of kept slots of the stream with a smaller id (equal ids,
+// which a bank never holds, in slot order).  Slots go through in chunks of 1024, one thread each; for every chunk of slots
+// the keys of every chunk pass through LDS and each thread counts the ones below its own -- all pairs, no atomics, and
+// every thread also counts the kept slots of the stream, so the padding rows are known without another pass.
+struct DrawKey {
+    int key;                                        // the id of a kept slot, -1 otherwise
+    float x1, y1, x2, y2;
+};
+
+__device__ __forceinline__ DrawKey draw_table_key(const float *__restrict__ boxes, const float *__restrict__ scores,
+                                                  const int64_t *__restrict__ ids, long i, int K, float ori_w,
+                                                  float ori_h, float score_thresh, float area_thresh) {
+    DrawKey r = {-1, 0.f, 0.f, 0.f, 0.f};
+    const int64_t id = ids[i];
+    if (id < 0 || id > 0x7fffffffLL) return r;
+    const KeptTrack t = kept_track(boxes, scores, i, K, ori_w, ori_h, score_thresh, area_thresh);
+    if (!t.keep) return r;
+    r.key = (int)id;
+    r.x1 = t.x1, r.y1 = t.y1, r.x2 = t.x2, r.y2 = t.y2;
+    return r;
+}
+
+// floor(v + 0.5) in float32, NaN -> 0, clamped to +-2^24 (render.track_table)
+__device__ __forceinline__ int draw_table_round(float v) {
+    const float r = floorf(__fadd_rn(v, 0.5f));
+    if (r != r) return 0;
+    return (int)fminf(fmaxf(r, -16777216.f), 16777216.f);
+}
+
+// render.palette_entry(i), i in 0 .. 63, as r | g << 8 | b << 16
+__device__ __forceinline__ int draw_table_palette(int i) {
+    const int hue = (i * 13 % 64) * 24, sector = hue >> 8, f = hue & 255;
+    const int lo = i % 3 == 0 ? 0 : (i % 3 == 1 ? 64 : 112);
+    const int up = lo + (255 - lo) * f / 255, down = lo + (255 - lo) * (255 - f) / 255;
+    int r, g, b;
+    switch (sector) {
+        case 0: r = 255, g = up, b = lo; break;
+        case 1: r = down, g = 255, b = lo; break;
+        case 2: r = lo, g = 255, b = up; break;
+        case 3: r = lo, g = down, b = 255; break;
+        case 4: r = up, g = lo, b = 255; break;
+        default: r = 255, g = lo, b = down; break;
+    }
+    return r | g << 8 | b << 16;
+}
+
+constexpr int DRAW_ROW_WORDS = 16;                  // TRACKDRAW_ROW_WORDS of include/track_draw_hip.h
+
+__global__ __launch_bounds__(BANK_THREADS) void draw_table_kernel(const float *__restrict__ boxes,
+                                                                  const float *__restrict__ scores,
+                                                                  const int64_t *__restrict__ ids, int cap, int K,
+                                                                  const float *__restrict__ ori_wh, float score_thresh,
+                                                                  float area_thresh, int bgr, int font_scale,
+                                                                  int32_t *__restrict__ table) {
+    __shared__ int4 keys4[BANK_THREADS / 4];
+    int *keys = reinterpret_cast<int *>(keys4);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long bc = (long)b * cap;
+    const float ori_w = ori_wh[2 * b], ori_h = ori_wh[2 * b + 1];
+    int32_t *rows = table + bc * DRAW_ROW_WORDS;
+    int total = 0;                                  // kept slots of the stream (every thread counts them all)
+    for (int i0 = 0; i0 < cap; i0 += BANK_THREADS) {             // (cap is uniform: every thread makes every trip)
+        const int i = i0 + tid;
+        DrawKey mine = {-1, 0.f, 0.f, 0.f, 0.f};
+        if (i < cap) mine = draw_table_key(boxes, scores, ids, bc + i, K, ori_w, ori_h, score_thresh, area_thresh);
+        int rank = 0;
+        total = 0;
+        for (int j0 = 0; j0 < cap; j0 += BANK_THREADS) {
+            int kj = mine.key;
+            if (j0 != i0) {
+                const int j = j0 + tid;
+                kj = j < cap ? draw_table_key(boxes, scores, ids, bc + j, K, ori_w, ori_h, score_thresh, area_thresh).key
+                             : -1;
+            }
+            keys[tid] = kj;
+            __syncthreads();
+            const int nj4 = (min(BANK_THREADS, cap - j0) + 3) >> 2;     // (every thread wrote a key: -1 past cap)
+#pragma unroll 4
+            for (int q = 0; q < nj4; ++q) {         // four keys a read: the loop is a chain of LDS latencies otherwise
+                const int4 k4 = keys4[q];
+                const int k[4] = {k4.x, k4.y, k4.z, k4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    total += k[e] >= 0;
+                    rank += k[e] >= 0 && (k[e] < mine.key || (k[e] == mine.key && j0 + 4 * q + e < i));
+                }
+            }
+            __syncthreads();                        // keys is written again by the next chunk
+        }
+        if (mine.key < 0) continue;
+        const int id = mine.key;
+        const int x1 = draw_table_round(mine.x1), y1 = draw_table_round(mine.y1);
+        const int rgb = draw_table_palette(id & 63);
+        const int r = rgb & 255, g = (rgb >> 8) & 255, bl = rgb >> 16;
+        int n_digits = 1;
+        for (int v = id; v >= 10; v /= 10) ++n_digits;
+        unsigned lo_word = 0, hi_word = 0;          // glyph k is the k-th digit from the left
+        for (int k = n_digits - 1, v = id; k >= 0; --k, v /= 10) {
+            const unsigned d = (unsigned)(v % 10);
+            if (k < 8) lo_word |= d << (4 * k);
+            else hi_word |= d << (4 * (k - 8));
+        }
+        const int tab_w = (6 * n_digits - 1) * font_scale + 2, tab_h = 7 * font_scale + 2;
+        const int ty1 = y1 - tab_h >= 0 ? y1 - tab_h : y1;
+        const int tx1 = min(x1, (int)ori_w - tab_w);
+        int32_t *row = rows + (long)rank * DRAW_ROW_WORDS;
+        row[0] = x1, row[1] = y1, row[2] = draw_table_round(mine.x2), row[3] = draw_table_round(mine.y2);
+        row[4] = bgr ? (bl | g << 8 | r << 16) : rgb;
+        row[5] = tx1, row[6] = ty1, row[7] = tx1 + tab_w - 1, row[8] = ty1 + tab_h - 1;
+        row[9] = ((77 * r + 150 * g + 29 * bl) >> 8) >= 128 ? 0 : 0xFFFFFF;
+        row[10] = n_digits, row[11] = (int32_t)lo_word, row[12] = (int32_t)hi_word;
+        row[13] = row[14] = row[15] = 0;
+    }
+    for (int p = total + tid; p < cap; p += BANK_THREADS) {      // the rows that draw nothing: x2 < x1
+        int32_t *row = rows + (long)p * DRAW_ROW_WORDS;
+        for (int k = 0; k < DRAW_ROW_WORDS; ++k) row[k] = (k == 2 || k == 3) ? -1 : 0;
+    }
+}
+}  // namespace
+
+extern "C" {
+int clipops_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels, int n,
+                            int K, int64_t frame, float ori_w, float ori_h, float score_thresh, float area_thresh,
+                            float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream) {
+    if (n < 0 || capacity < 0) return fail(1, "clipops_result_rows_f32: negative size");
+    if (K < 1) return fail(1, "clipops_result_rows_f32: K < 1");
+    if (n == 0) return ok();
+    if (!boxes || !scores || !ids || !labels || !counters || (capacity > 0 && (!rows_f || !rows_i)))
+        return fail(1, "clipops_result_rows_f32: null pointer");
+    return launch("result_rows_kernel", result_rows_kernel, dim3(1), dim3(256), 0, stream, boxes, scores, ids, labels, n, K,
+                  frame, ori_w, ori_h, score_thresh, area_thresh, rows_f, rows_i, counters, capacity) ? 3 : 0;
+}
+
+int clipops_bank_update_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap, int K,
+                            int C, int use_dab, float det_score_thresh, float track_score_thresh,
+                            int64_t miss_tolerance, void *stream) {
+    if (B < 0 || n_det < 0 || cap < 0) return fail(1, "clipops_bank_update_f32: negative size");
+    if (K < 1 || C < 1) return fail(1, "clipops_bank_update_f32: K < 1 or C < 1");
+    if (cap < 1) return fail(1, "clipops_bank_update_f32: a bank without slots");
+    if (B == 0) return ok();
+    if (!model || !bank) return fail(1, "clipops_bank_update_f32: null pointer");
+    for (int i = 0; i < CLIPOPS_BK_N_MODEL; ++i) {
+        if (!model->ptr[i]) return fail(1, "clipops_bank_update_f32: null model pointer");
+        if (model->row_stride[i] < 0 || model->batch_stride[i] < 0)
+            return fail(1, "clipops_bank_update_f32: negative stride");
+    }
+    if (!use_dab && (!model->det_embed || model->det_row_stride < 0))
+        return fail(1, "clipops_bank_update_f32: det_embed is required without DAB");
+    if (!bank->ids || !bank->labels || !bank->disappear_time || !bank->boxes || !bank->ref_pts || !bank->logits ||
+        !bank->scores || !bank->output_embed || !bank->long_memory || !bank->last_output || !bank->query_embed ||
+        !bank->next_id || !bank->counters || !bank->free_list)
+        return fail(1, "clipops_bank_update_f32: null bank pointer");
+    return launch("bank_update_kernel", bank_update_kernel, dim3(B), dim3(BANK_THREADS), 0, stream, *model, *bank, n_det,
+                  cap, K, C, use_dab, det_score_thresh, track_score_thresh, miss_tolerance) ? 3 : 0;
+}
+
+int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels,
+                                 int B, int cap, int K, const int64_t *seq_frame, const float *ori_wh,
+                                 float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
+                                 int32_t *counters, int capacity, void *stream) {
+    if (B < 0 || cap < 0 || capacity < 0) return fail(1, "clipops_bank_result_rows_f32: negative size");
+    if (K < 1) return fail(1, "clipops_bank_result_rows_f32: K < 1");
+    if ((long)B * cap > 0x7fffffffL) return fail(1, "clipops_bank_result_rows_f32: more than 2^31 - 1 slots");
+    if ((long)B * cap == 0) return ok();
+    if (!boxes || !scores || !ids || !labels || !seq_frame || !ori_wh || !counters ||
+        (capacity > 0 && (!rows_f || !rows_i)))
+        return fail(1, "clipops_bank_result_rows_f32: null pointer");
+    return launch("bank_result_rows_kernel", bank_result_rows_kernel, dim3(1), dim3(256), 0, stream, boxes, scores, ids,
+                  labels, B * cap, cap, K, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters,
+                  capacity) ? 3 : 0;
+}
+
+int clipops_draw_table_f32(const float *boxes, const float *scores, const int64_t *ids, int B, int cap, int K,
+                           const float *ori_wh, float score_thresh, float area_thresh, int bgr, int font_scale,
+                           int32_t *table, void *stream) {
+    if (B < 0 || cap < 0) return fail(1, "clipops_draw_table_f32: negative size");
+    if (K < 1) return fail(1, "clipops_draw_table_f32: K < 1");
+    if (font_scale < 1 || font_scale > 64) return fail(1, "clipops_draw_table_f32: font_scale outside 1 .. 64");
+    if ((long)B * cap > 0x7fffffffL) return fail(1, "clipops_draw_table_f32: more than 2^31 - 1 slots");
+    if ((long)B * cap == 0) return ok();
+    if (!boxes || !scores || !ids || !ori_wh || !table) return fail(1, "clipops_draw_table_f32: null pointer");
+    return launch("draw_table_kernel", draw_table_kernel, dim3(B), dim3(BANK_THREADS), 0, stream, boxes, scores, ids, cap,
+                  K, ori_wh, score_thresh, area_thresh, bgr ? 1 : 0, font_scale, table) ? 3 : 0;
+}
+}  // extern "C"

@@ -16,7 +16,8 @@ CSRC = os.path.join(ROOT, "memotr_amd", "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 # what each library was declared to depend on when the lists were written by hand: csrc/ names, include/ names
 HAND_WRITTEN = {
-    "clip": (["clip_ops.hip", "assign_core.h"], ["clip_ops_hip.h"]),
+    "clip": (["clip_ops.hip", "assign_core.h", "clip_common.h", "clip_criterion.h", "clip_handover.h", "clip_boxes.h",
+              "clip_rows.h", "clip_attention.h", "clip_linear.h", "clip_tracks.h", "clip_fill_gaps.h"], ["clip_ops_hip.h"]),
     "frame": (["frame_ops.hip"], ["frame_ops_hip.h"]),
     "augment": (["augment_ops.hip"], ["augment_ops_hip.h"]),
     "static_clip": (["static_clip_ops.hip"], ["static_clip_ops_hip.h"]),

@@ -1,4 +1,4 @@
-"""GPU: ``clipops_draw_table_f32`` (memotr_amd/csrc/clip_ops.hip) against ``clip_ops.draw_table_reference`` to the bit
+"""GPU: ``clipops_draw_table_f32`` (memotr_amd/csrc/clip_tracks.h) against ``clip_ops.draw_table_reference`` to the bit
 on the cases of tests/draw_table_cases.py, across the 1024-slot chunk, and through the overlay kernel: the padded device
 table drawn with ``n = cap`` gives the frame ``draw_table_host`` draws from the compact host table."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU: ``ResultLog.filled`` / ``BankResultLog.filled`` (clipops_fill_gaps_f32, memotr_amd/csrc/clip_ops.hip) against
+"""GPU: ``ResultLog.filled`` / ``BankResultLog.filled`` (clipops_fill_gaps_f32, memotr_amd/csrc/clip_fill_gaps.h) against
 the host statement (memotr_amd/postprocess.py ``fill_gaps``), bit for bit: table sizes at the wavefront and chunk edges
 of the scans and ranks, holes across those edges, bank tables, the capacity rule with guard words, the status bits, and
 tracking runs and ``submit`` with the pass on."""

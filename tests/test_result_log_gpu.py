@@ -1,4 +1,4 @@
-"""GPU: the result-row kernel (clipops_result_rows_f32, memotr_amd/csrc/clip_ops.hip) against the host statement
+"""GPU: the result-row kernel (clipops_result_rows_f32, memotr_amd/csrc/clip_tracks.h) against the host statement
 (memotr_amd/results.py:host_rows through a CPU ``ResultLog``), bit for bit: every keep pattern at the lane, wavefront
 and chunk edges, input order, appending, the capacity rule with guard words behind the tables, growth, ties and NaN;
 and ``SequenceTracker.track_logged`` + ``ResultLog.mot_lines`` against ``track`` / ``track_jpeg`` + ``mot_lines``, byte

@@ -1,4 +1,4 @@
-"""GPU: the two track-bank kernels (clipops_bank_update_f32, clipops_bank_result_rows_f32, memotr_amd/csrc/clip_ops.hip)
+"""GPU: the two track-bank kernels (clipops_bank_update_f32, clipops_bank_result_rows_f32, memotr_amd/csrc/clip_tracks.h)
 against their host statements (memotr_amd/functions/clip_ops.py: bank_update_reference on the same device tensors --
 torch's sigmoid there is the kernel's 1 / (1 + expf(-x)) -- and bank_result_rows_reference on the CPU, whose float32
 arithmetic is exact), bit for bit: one and three streams, detect-row counts around the 64-lane and 256-thread edges, banks
