@@ -389,6 +389,24 @@ int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const 
                                  float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
                                  int32_t *counters, int capacity, void *stream);
 
+/* ---- the bank entries with one threshold per stream: one sequence tracked under B settings at once ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the bank entries: no entry point changed.)
+ * clipops_bank_update_f32 / clipops_bank_result_rows_f32 with every threshold a device array of B values (float32;
+ * miss_tolerance int64), stream b applying element b.  Stream b of a _streams call equals, bit for bit, stream b of the
+ * scalar call made with that stream's values -- every bank field, next_id, counters, free_list, the rows and their order
+ * in the table: the same kernels read the value from the array where the scalar entries take it from the argument, and
+ * make the same float32 comparisons in the same order (>= for a birth, < for a miss, strict > in the result filter, a
+ * NaN score as before).  In the update one workgroup is one stream and loads its three values once; the result rows
+ * read the two values of slot / cap per slot.  The arrays are read on `stream`; no atomics.  Arguments are checked as
+ * the scalar entries check theirs, then: returns 1 for a null threshold array.  B == 0 launches nothing. */
+int clipops_bank_update_streams_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap,
+                                    int K, int C, int use_dab, const float *det_score_thresh,
+                                    const float *track_score_thresh, const int64_t *miss_tolerance, void *stream);
+int clipops_bank_result_rows_streams_f32(const float *boxes, const float *scores, const int64_t *ids,
+                                         const int64_t *labels, int B, int cap, int K, const int64_t *seq_frame,
+                                         const float *ori_wh, const float *score_thresh, const float *area_thresh,
+                                         float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream);
+
 /* ---- the overlay's draw table, made on the device from the tracks where they live ----
  * (Added without a new CLIPOPS_ABI_VERSION, like the bank entries: no entry point changed.)
  * The int32 table trackdraw_draw_u8 draws from (include/track_draw_hip.h: 16 words a row), for every stream of a bank

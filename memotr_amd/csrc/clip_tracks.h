@@ -101,12 +101,44 @@ __global__ __launch_bounds__(256) void result_rows_kernel(const float *__restric
 // (16 wavefronts: phase 2 is a chain of dependent loads per slot, and a wavefront walks its slots one after another)
 constexpr int BANK_THREADS = 1024, BANK_WAVES = BANK_THREADS / 64;
 
+// Where a bank kernel's thresholds come from: one value for every stream (the scalar entry points) or an array with one
+// value per stream (the _streams entry points: a threshold sweep runs one sequence under B settings).  Both give the
+// kernels the same float32 / int64 values to compare against, so stream b of a _streams call has the bits of the scalar
+// call made with stream b's values.
+struct BankUpdateScalars {
+    float det_v, track_v;
+    int64_t miss_v;
+    __device__ __forceinline__ float det(int) const { return det_v; }
+    __device__ __forceinline__ float track(int) const { return track_v; }
+    __device__ __forceinline__ int64_t miss(int) const { return miss_v; }
+};
+struct BankUpdatePerStream {
+    const float *det_a, *track_a;
+    const int64_t *miss_a;
+    __device__ __forceinline__ float det(int b) const { return det_a[b]; }
+    __device__ __forceinline__ float track(int b) const { return track_a[b]; }
+    __device__ __forceinline__ int64_t miss(int b) const { return miss_a[b]; }
+};
+struct BankRowsScalars {
+    float score_v, area_v;
+    __device__ __forceinline__ float score(int) const { return score_v; }
+    __device__ __forceinline__ float area(int) const { return area_v; }
+};
+struct BankRowsPerStream {
+    const float *score_a, *area_a;
+    __device__ __forceinline__ float score(int b) const { return score_a[b]; }
+    __device__ __forceinline__ float area(int b) const { return area_a[b]; }
+};
+
+template <typename Thresholds>
 __global__ __launch_bounds__(BANK_THREADS) void bank_update_kernel(clipops_bank_model m, clipops_bank bank, int n_det, int cap,
-                                                          int K, int C, int use_dab, float det_thresh,
-                                                          float track_thresh, int64_t miss_tolerance) {
+                                                          int K, int C, int use_dab, Thresholds th) {
 #pragma clang fp contract(off)
     __shared__ int wave_total[BANK_WAVES], wave_live[BANK_WAVES], pair_row[BANK_THREADS], pair_slot[BANK_THREADS];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (one workgroup is one stream: the three values are uniform over it and read once)
+    const float det_thresh = th.det(b), track_thresh = th.track(b);
+    const int64_t miss_tolerance = th.miss(b);
     const int QW = use_dab ? C : 2 * C;
     const long bc = (long)b * cap;
     int64_t *ids = bank.ids + bc, *labels = bank.labels + bc, *dtime = bank.disappear_time + bc;
@@ -240,14 +272,16 @@ __global__ __launch_bounds__(BANK_THREADS) void bank_update_kernel(clipops_bank_
 }
 
 // clipops_result_rows_f32's filter and arithmetic over the B * cap slots of a bank, streams in order, free slots skipped:
-// one workgroup, so that the rows of all streams land in one table in a fixed order.
+// one workgroup, so that the rows of all streams land in one table in a fixed order.  The stream of a slot is
+// slot / cap, and the two thresholds are that stream's.
+template <typename Thresholds>
 __global__ __launch_bounds__(256) void bank_result_rows_kernel(const float *__restrict__ boxes,
                                                                const float *__restrict__ scores,
                                                                const int64_t *__restrict__ ids,
                                                                const int64_t *__restrict__ labels, int n_slots, int cap,
                                                                int K, const int64_t *__restrict__ seq_frame,
-                                                               const float *__restrict__ ori_wh, float score_thresh,
-                                                               float area_thresh, float *__restrict__ rows_f,
+                                                               const float *__restrict__ ori_wh, Thresholds th,
+                                                               float *__restrict__ rows_f,
                                                                int64_t *__restrict__ rows_i,
                                                                int32_t *__restrict__ counters, int capacity) {
     __shared__ int wave_total[4];
@@ -260,7 +294,7 @@ __global__ __launch_bounds__(256) void bank_result_rows_kernel(const float *__re
         int b = 0;
         if (i < n_slots && ids[i] >= 0) {
             b = i / cap;
-            t = kept_track(boxes, scores, i, K, ori_wh[2 * b], ori_wh[2 * b + 1], score_thresh, area_thresh);
+            t = kept_track(boxes, scores, i, K, ori_wh[2 * b], ori_wh[2 * b + 1], th.score(b), th.area(b));
         }
         int before, total;
         bank_ranks<4>(t.keep, lane, wave, wave_total, before, total);
@@ -401,6 +435,40 @@ __global__ __launch_bounds__(BANK_THREADS) void draw_table_kernel(const float *_
         for (int k = 0; k < DRAW_ROW_WORDS; ++k) row[k] = (k == 2 || k == 3) ? -1 : 0;
     }
 }
+// The argument checks the scalar and the per-stream entry points of the bank share, reported under the caller's name:
+// 1 = launch, 0 = nothing to do (ok() is set), -code = fail()'s code.
+int bank_update_args(const char *who, const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap,
+                     int K, int C, int use_dab) {
+    if (B < 0 || n_det < 0 || cap < 0) return -fail(1, who, "negative size");
+    if (K < 1 || C < 1) return -fail(1, who, "K < 1 or C < 1");
+    if (cap < 1) return -fail(1, who, "a bank without slots");
+    if (B == 0) return ok();
+    if (!model || !bank) return -fail(1, who, "null pointer");
+    for (int i = 0; i < CLIPOPS_BK_N_MODEL; ++i) {
+        if (!model->ptr[i]) return -fail(1, who, "null model pointer");
+        if (model->row_stride[i] < 0 || model->batch_stride[i] < 0) return -fail(1, who, "negative stride");
+    }
+    if (!use_dab && (!model->det_embed || model->det_row_stride < 0))
+        return -fail(1, who, "det_embed is required without DAB");
+    if (!bank->ids || !bank->labels || !bank->disappear_time || !bank->boxes || !bank->ref_pts || !bank->logits ||
+        !bank->scores || !bank->output_embed || !bank->long_memory || !bank->last_output || !bank->query_embed ||
+        !bank->next_id || !bank->counters || !bank->free_list)
+        return -fail(1, who, "null bank pointer");
+    return 1;
+}
+
+int bank_rows_args(const char *who, const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels,
+                   int B, int cap, int K, const int64_t *seq_frame, const float *ori_wh, const float *rows_f,
+                   const int64_t *rows_i, const int32_t *counters, int capacity) {
+    if (B < 0 || cap < 0 || capacity < 0) return -fail(1, who, "negative size");
+    if (K < 1) return -fail(1, who, "K < 1");
+    if ((long)B * cap > 0x7fffffffL) return -fail(1, who, "more than 2^31 - 1 slots");
+    if ((long)B * cap == 0) return ok();
+    if (!boxes || !scores || !ids || !labels || !seq_frame || !ori_wh || !counters ||
+        (capacity > 0 && (!rows_f || !rows_i)))
+        return -fail(1, who, "null pointer");
+    return 1;
+}
 }  // namespace
 
 extern "C" {
@@ -419,39 +487,52 @@ int clipops_result_rows_f32(const float *boxes, const float *scores, const int64
 int clipops_bank_update_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap, int K,
                             int C, int use_dab, float det_score_thresh, float track_score_thresh,
                             int64_t miss_tolerance, void *stream) {
-    if (B < 0 || n_det < 0 || cap < 0) return fail(1, "clipops_bank_update_f32: negative size");
-    if (K < 1 || C < 1) return fail(1, "clipops_bank_update_f32: K < 1 or C < 1");
-    if (cap < 1) return fail(1, "clipops_bank_update_f32: a bank without slots");
-    if (B == 0) return ok();
-    if (!model || !bank) return fail(1, "clipops_bank_update_f32: null pointer");
-    for (int i = 0; i < CLIPOPS_BK_N_MODEL; ++i) {
-        if (!model->ptr[i]) return fail(1, "clipops_bank_update_f32: null model pointer");
-        if (model->row_stride[i] < 0 || model->batch_stride[i] < 0)
-            return fail(1, "clipops_bank_update_f32: negative stride");
-    }
-    if (!use_dab && (!model->det_embed || model->det_row_stride < 0))
-        return fail(1, "clipops_bank_update_f32: det_embed is required without DAB");
-    if (!bank->ids || !bank->labels || !bank->disappear_time || !bank->boxes || !bank->ref_pts || !bank->logits ||
-        !bank->scores || !bank->output_embed || !bank->long_memory || !bank->last_output || !bank->query_embed ||
-        !bank->next_id || !bank->counters || !bank->free_list)
-        return fail(1, "clipops_bank_update_f32: null bank pointer");
-    return launch("bank_update_kernel", bank_update_kernel, dim3(B), dim3(BANK_THREADS), 0, stream, *model, *bank, n_det,
-                  cap, K, C, use_dab, det_score_thresh, track_score_thresh, miss_tolerance) ? 3 : 0;
+    const char *who = "clipops_bank_update_f32";
+    const int todo = bank_update_args(who, model, bank, B, n_det, cap, K, C, use_dab);
+    if (todo <= 0) return -todo;
+    const BankUpdateScalars th = {det_score_thresh, track_score_thresh, miss_tolerance};
+    return launch("bank_update_kernel", bank_update_kernel<BankUpdateScalars>, dim3(B), dim3(BANK_THREADS), 0, stream,
+                  *model, *bank, n_det, cap, K, C, use_dab, th) ? 3 : 0;
+}
+
+int clipops_bank_update_streams_f32(const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap,
+                                    int K, int C, int use_dab, const float *det_score_thresh,
+                                    const float *track_score_thresh, const int64_t *miss_tolerance, void *stream) {
+    const char *who = "clipops_bank_update_streams_f32";
+    const int todo = bank_update_args(who, model, bank, B, n_det, cap, K, C, use_dab);
+    if (todo <= 0) return -todo;
+    if (!det_score_thresh || !track_score_thresh || !miss_tolerance) return fail(1, who, "null threshold array");
+    const BankUpdatePerStream th = {det_score_thresh, track_score_thresh, miss_tolerance};
+    return launch("bank_update_kernel", bank_update_kernel<BankUpdatePerStream>, dim3(B), dim3(BANK_THREADS), 0, stream,
+                  *model, *bank, n_det, cap, K, C, use_dab, th) ? 3 : 0;
 }
 
 int clipops_bank_result_rows_f32(const float *boxes, const float *scores, const int64_t *ids, const int64_t *labels,
                                  int B, int cap, int K, const int64_t *seq_frame, const float *ori_wh,
                                  float score_thresh, float area_thresh, float *rows_f, int64_t *rows_i,
                                  int32_t *counters, int capacity, void *stream) {
-    if (B < 0 || cap < 0 || capacity < 0) return fail(1, "clipops_bank_result_rows_f32: negative size");
-    if (K < 1) return fail(1, "clipops_bank_result_rows_f32: K < 1");
-    if ((long)B * cap > 0x7fffffffL) return fail(1, "clipops_bank_result_rows_f32: more than 2^31 - 1 slots");
-    if ((long)B * cap == 0) return ok();
-    if (!boxes || !scores || !ids || !labels || !seq_frame || !ori_wh || !counters ||
-        (capacity > 0 && (!rows_f || !rows_i)))
-        return fail(1, "clipops_bank_result_rows_f32: null pointer");
-    return launch("bank_result_rows_kernel", bank_result_rows_kernel, dim3(1), dim3(256), 0, stream, boxes, scores, ids,
-                  labels, B * cap, cap, K, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters,
+    const char *who = "clipops_bank_result_rows_f32";
+    const int todo = bank_rows_args(who, boxes, scores, ids, labels, B, cap, K, seq_frame, ori_wh, rows_f, rows_i,
+                                    counters, capacity);
+    if (todo <= 0) return -todo;
+    const BankRowsScalars th = {score_thresh, area_thresh};
+    return launch("bank_result_rows_kernel", bank_result_rows_kernel<BankRowsScalars>, dim3(1), dim3(256), 0, stream,
+                  boxes, scores, ids, labels, B * cap, cap, K, seq_frame, ori_wh, th, rows_f, rows_i, counters,
+                  capacity) ? 3 : 0;
+}
+
+int clipops_bank_result_rows_streams_f32(const float *boxes, const float *scores, const int64_t *ids,
+                                         const int64_t *labels, int B, int cap, int K, const int64_t *seq_frame,
+                                         const float *ori_wh, const float *score_thresh, const float *area_thresh,
+                                         float *rows_f, int64_t *rows_i, int32_t *counters, int capacity, void *stream) {
+    const char *who = "clipops_bank_result_rows_streams_f32";
+    const int todo = bank_rows_args(who, boxes, scores, ids, labels, B, cap, K, seq_frame, ori_wh, rows_f, rows_i,
+                                    counters, capacity);
+    if (todo <= 0) return -todo;
+    if (!score_thresh || !area_thresh) return fail(1, who, "null threshold array");
+    const BankRowsPerStream th = {score_thresh, area_thresh};
+    return launch("bank_result_rows_kernel", bank_result_rows_kernel<BankRowsPerStream>, dim3(1), dim3(256), 0, stream,
+                  boxes, scores, ids, labels, B * cap, cap, K, seq_frame, ori_wh, th, rows_f, rows_i, counters,
                   capacity) ? 3 : 0;
 }
 

@@ -1007,6 +1007,28 @@ def _bank_model_tensors(res: dict, bank, use_dab: bool):
     return named, det, n_det
 
 
+def _bank_update_structs(L, named, det, bank):
+    """``(clipops_bank_model, clipops_bank, tensors to keep alive)`` of a bank update's launch."""
+    model, keep = L.BankModel(), []
+    for i, name in enumerate(L.BANK_MODEL):
+        t = named[name].detach()
+        if t.shape[2] > 1 and t.stride(2) != 1 or t.stride(0) < 0 or t.stride(1) < 0:
+            t = t.contiguous()
+        keep.append(t)
+        model.ptr[i], model.batch_stride[i], model.row_stride[i] = t.data_ptr(), t.stride(0), t.stride(1)
+    if det is not None:
+        det = _rows_dense(det.detach())
+        keep.append(det)
+        model.det_embed, model.det_row_stride = det.data_ptr(), det.stride(0)
+    table = L.Bank()
+    for name in L.BANK_FIELDS:
+        t = getattr(bank, name)
+        if not t.is_contiguous():
+            raise RuntimeError(f"bank update: the bank's {name} is not contiguous")
+        setattr(table, name, t.data_ptr())
+    return model, table, keep
+
+
 def bank_update(res: dict, bank, det_score_thresh: float, track_score_thresh: float, miss_tolerance: int) -> None:
     """One frame of track management for every stream of ``bank`` (a ``TrackBank``), in place and without a read-back:
     ``RuntimeTracker.update`` plus the inference branch of ``QueryUpdater.select_active_tracks`` on slot tables (see
@@ -1018,22 +1040,7 @@ def bank_update(res: dict, bank, det_score_thresh: float, track_score_thresh: fl
     if not bank.ids.is_cuda:
         return bank_update_reference(res, bank, det_score_thresh, track_score_thresh, miss_tolerance)
     L = _lib()
-    model, keep = L.BankModel(), []
-    for i, name in enumerate(L.BANK_MODEL):
-        t = named[name].detach()
-        if t.shape[2] > 1 and t.stride(2) != 1 or t.stride(0) < 0 or t.stride(1) < 0:
-            t = t.contiguous()
-        keep.append(t)
-        model.ptr[i], model.batch_stride[i], model.row_stride[i] = t.data_ptr(), t.stride(0), t.stride(1)
-    if det is not None:
-        det = _rows_dense(det.detach())
-        model.det_embed, model.det_row_stride = det.data_ptr(), det.stride(0)
-    table = L.Bank()
-    for name in L.BANK_FIELDS:
-        t = getattr(bank, name)
-        if not t.is_contiguous():
-            raise RuntimeError(f"bank update: the bank's {name} is not contiguous")
-        setattr(table, name, t.data_ptr())
+    model, table, keep = _bank_update_structs(L, named, det, bank)
     L.check(L.lib.clipops_bank_update_f32(
         ctypes.byref(model), ctypes.byref(table), bank.n_streams, n_det, bank.cap, bank.num_classes, bank.hidden_dim,
         int(bank.use_dab), float(det_score_thresh), float(track_score_thresh), int(miss_tolerance), _stream(bank.ids)),
@@ -1095,12 +1102,85 @@ def bank_update_reference(res: dict, bank, det_score_thresh: float, track_score_
         bank.counters[b, 1] += int(born.shape[0]) - placed
 
 
-def bank_result_rows(bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float, area_thresh: float,
-                     rows_f: torch.Tensor, rows_i: torch.Tensor, counters: torch.Tensor) -> None:
-    """The reportable rows of every stream's live tracks behind the rows already in the table (``rows_f`` (capacity, 5)
-    float32, ``rows_i`` (capacity, 4) int64: sequence, frame, id, label; ``counters`` (2,) int32: stored, dropped) -- one
-    launch, nothing read back.  ``seq_frame`` int64 (B, 2) and ``ori_wh`` float32 (B, 2) = (ori_w, ori_h) per stream,
-    on the bank's device.  CPU tensors run ``bank_result_rows_reference``."""
+class StreamThresholds:
+    """One setting per stream of a bank, as the device arrays the ``_streams`` entry points read: ``det``, ``track``,
+    ``result``, ``area`` float32 (S,) and ``miss`` int64 (S,).  Built once per sweep; ``settings`` keeps the host values
+    (``det_score_thresh``, ``track_score_thresh``, ``result_score_thresh``, ``miss_tolerance``, ``area_thresh``), which
+    the host statements and the per-frame report read, so that nothing is read back from the arrays."""
+
+    KEYS = ("det_score_thresh", "track_score_thresh", "result_score_thresh", "miss_tolerance")
+
+    def __init__(self, settings, device, area_thresh: float = 100):
+        settings = [dict(s) for s in settings]
+        if not settings:
+            raise ValueError("stream thresholds: at least one setting")
+        for k, s in enumerate(settings):
+            s.setdefault("area_thresh", area_thresh)
+            unknown = sorted(set(s) - set(self.KEYS) - {"area_thresh"})
+            missing = [key for key in self.KEYS if key not in s]
+            if unknown or missing:
+                raise ValueError(f"stream thresholds: setting {k} " + (f"has unknown keys {unknown}" if unknown else
+                                                                        f"lacks {missing}"))
+        self.settings = settings
+        self.device = torch.device(device)
+        col = lambda key, dtype: torch.tensor([s[key] for s in settings], dtype=dtype).to(self.device)   # noqa: E731
+        self.det, self.track = col("det_score_thresh", torch.float32), col("track_score_thresh", torch.float32)
+        self.result, self.area = col("result_score_thresh", torch.float32), col("area_thresh", torch.float32)
+        self.miss = col("miss_tolerance", torch.int64)
+        self.device = self.det.device                   # ("cuda" -> the current device, by name)
+
+    def __len__(self) -> int:
+        return len(self.settings)
+
+    def _check(self, bank, what: str) -> None:
+        if len(self) != bank.n_streams or self.device != bank.ids.device:
+            raise ValueError(f"{what}: {len(self)} settings on {self.device} for a bank of {bank.n_streams} streams on "
+                             f"{bank.ids.device}")
+
+
+def _one_stream(res: dict, bank, b: int):
+    """Stream ``b`` of a bank and of the model's outputs as a bank of one stream: views, so writes land in ``bank``."""
+    import copy
+    from ..models.track_bank import STREAM_FIELDS
+    one = copy.copy(bank)
+    for name in STREAM_FIELDS:
+        setattr(one, name, getattr(bank, name)[b:b + 1])
+    one.n_streams = 1
+    if res is None:
+        return None, one
+    part = {name: res[name][b:b + 1] for name in ("pred_logits", "pred_bboxes", "outputs", "last_ref_pts")}
+    part["aux_outputs"] = [{"queries": res["aux_outputs"][-1]["queries"][b:b + 1]}]
+    if "det_query_embed" in res:
+        part["det_query_embed"] = res["det_query_embed"]
+    return part, one
+
+
+def bank_update_streams(res: dict, bank, thresholds: StreamThresholds) -> None:
+    """``bank_update`` with stream b under setting b of ``thresholds``: one launch of clipops_bank_update_streams_f32,
+    whose stream b has the bits of ``bank_update`` made with that stream's values.  CPU tensors run
+    ``bank_update_streams_reference``."""
+    thresholds._check(bank, "bank update")
+    named, det, n_det = _bank_model_tensors(res, bank, bank.use_dab)
+    if not bank.ids.is_cuda:
+        return bank_update_streams_reference(res, bank, thresholds)
+    L = _lib()
+    model, table, keep = _bank_update_structs(L, named, det, bank)
+    L.check(L.lib.clipops_bank_update_streams_f32(
+        ctypes.byref(model), ctypes.byref(table), bank.n_streams, n_det, bank.cap, bank.num_classes, bank.hidden_dim,
+        int(bank.use_dab), thresholds.det.data_ptr(), thresholds.track.data_ptr(), thresholds.miss.data_ptr(),
+        _stream(bank.ids)), "clipops_bank_update_streams_f32")
+
+
+@torch.no_grad()
+def bank_update_streams_reference(res: dict, bank, thresholds: StreamThresholds) -> None:
+    """``bank_update_reference`` stream by stream, each with its own setting (what CPU tensors run)."""
+    thresholds._check(bank, "bank update")
+    for b, s in enumerate(thresholds.settings):
+        part, one = _one_stream(res, bank, b)
+        bank_update_reference(part, one, s["det_score_thresh"], s["track_score_thresh"], s["miss_tolerance"])
+
+
+def _bank_rows_args(bank, seq_frame, ori_wh, rows_f, rows_i, counters) -> None:
     B, capacity = bank.n_streams, rows_f.shape[0]
     if (seq_frame.dtype != torch.int64 or tuple(seq_frame.shape) != (B, 2) or ori_wh.dtype != torch.float32
             or tuple(ori_wh.shape) != (B, 2)):
@@ -1110,6 +1190,46 @@ def bank_result_rows(bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_
             or tuple(rows_i.shape) != (capacity, 4) or counters.dtype != torch.int32 or counters.numel() != 2):
         raise ValueError("bank result rows: the table is rows_f (capacity, 5) float32, rows_i (capacity, 4) int64, "
                          "counters (2,) int32")
+
+
+def bank_result_rows_streams(bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, thresholds: StreamThresholds,
+                             rows_f: torch.Tensor, rows_i: torch.Tensor, counters: torch.Tensor) -> None:
+    """``bank_result_rows`` with stream b filtered by ``thresholds.result[b]`` and ``thresholds.area[b]``: one launch of
+    clipops_bank_result_rows_streams_f32.  CPU tensors run ``bank_result_rows_streams_reference``."""
+    thresholds._check(bank, "bank result rows")
+    _bank_rows_args(bank, seq_frame, ori_wh, rows_f, rows_i, counters)
+    if not bank.ids.is_cuda:
+        return bank_result_rows_streams_reference(bank, seq_frame, ori_wh, thresholds, rows_f, rows_i, counters)
+    for t in (bank.boxes, bank.scores, bank.ids, bank.labels, seq_frame, ori_wh, rows_f, rows_i, counters,
+              thresholds.result, thresholds.area):
+        if not t.is_contiguous() or t.device != bank.ids.device:
+            raise RuntimeError("bank result rows: every tensor is contiguous and on the bank's device")
+    L = _lib()
+    L.check(L.lib.clipops_bank_result_rows_streams_f32(
+        bank.boxes.data_ptr(), bank.scores.data_ptr(), bank.ids.data_ptr(), bank.labels.data_ptr(), bank.n_streams,
+        bank.cap, bank.num_classes, seq_frame.data_ptr(), ori_wh.data_ptr(), thresholds.result.data_ptr(),
+        thresholds.area.data_ptr(), rows_f.data_ptr(), rows_i.data_ptr(), counters.data_ptr(), rows_f.shape[0],
+        _stream(bank.ids)), "clipops_bank_result_rows_streams_f32")
+
+
+@torch.no_grad()
+def bank_result_rows_streams_reference(bank, seq_frame, ori_wh, thresholds, rows_f, rows_i, counters) -> None:
+    """``bank_result_rows_reference`` stream by stream, each with its own setting (what CPU tensors run)."""
+    thresholds._check(bank, "bank result rows")
+    for b, s in enumerate(thresholds.settings):
+        _, one = _one_stream(None, bank, b)
+        bank_result_rows_reference(one, seq_frame[b:b + 1], ori_wh[b:b + 1], s["result_score_thresh"], s["area_thresh"],
+                                   rows_f, rows_i, counters)
+
+
+def bank_result_rows(bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, score_thresh: float, area_thresh: float,
+                     rows_f: torch.Tensor, rows_i: torch.Tensor, counters: torch.Tensor) -> None:
+    """The reportable rows of every stream's live tracks behind the rows already in the table (``rows_f`` (capacity, 5)
+    float32, ``rows_i`` (capacity, 4) int64: sequence, frame, id, label; ``counters`` (2,) int32: stored, dropped) -- one
+    launch, nothing read back.  ``seq_frame`` int64 (B, 2) and ``ori_wh`` float32 (B, 2) = (ori_w, ori_h) per stream,
+    on the bank's device.  CPU tensors run ``bank_result_rows_reference``."""
+    B, capacity = bank.n_streams, rows_f.shape[0]
+    _bank_rows_args(bank, seq_frame, ori_wh, rows_f, rows_i, counters)
     if not bank.ids.is_cuda:
         return bank_result_rows_reference(bank, seq_frame, ori_wh, score_thresh, area_thresh, rows_f, rows_i, counters)
     for t in (bank.boxes, bank.scores, bank.ids, bank.labels, seq_frame, ori_wh, rows_f, rows_i, counters):

@@ -187,7 +187,7 @@ class MultiSequenceTracker:
     @torch.no_grad()
     def _encoded(self, step: _Step, bgr: bool) -> dict:
         """Steps 1-2: this step's encode result -- the one queued ahead by the previous step, or computed now."""
-        if len(step.frames) != self.bank.n_streams:
+        if len(step.frames) != self._frames_per_step():
             raise ValueError(f"{len(step.frames)} frames for a bank of {self.bank.n_streams} streams")
         return self._lookahead.take(step, lambda s, after: self._batch_frame(s, bgr, after))
 
@@ -202,10 +202,22 @@ class MultiSequenceTracker:
             if nxt is not None:             # (uploads on the side stream first, then the wait for main)
                 self._lookahead.queue(nxt, lambda s, after: self._batch_frame(s, bgr, after), False,
                                       inputs=[nxt.batch] + nxt.frames)
-        clip_ops.bank_update(res, bank, self.det_score_thresh, self.track_score_thresh, self.miss_tolerance)
+        self._bank_update(res)
         self.core.query_updater.update_bank(bank)
         self._watch_counts()
         return nxt
+
+    # what a tracker of one sequence under several settings (inference_sweep.SweepTracker) states differently
+    def _frames_per_step(self) -> int:
+        return self.bank.n_streams
+
+    def _bank_update(self, res: dict) -> None:
+        """Step 4."""
+        clip_ops.bank_update(res, self.bank, self.det_score_thresh, self.track_score_thresh, self.miss_tolerance)
+
+    def _report_thresholds(self, b: int):
+        """``(result_score_thresh, area_thresh)`` of stream ``b``'s report."""
+        return self.result_score_thresh, self.area_thresh
 
     def _decode(self, enc: dict) -> dict:
         core, bank = self.core, self.bank
@@ -294,8 +306,8 @@ class MultiSequenceTracker:
             rows = host[b]
             ids = rows[:, 4 + K].long()
             slots = (ids >= 0).nonzero().squeeze(1)
-            out.append(reportable(rows[slots[torch.argsort(ids[slots])]], K, ori_h, ori_w, self.result_score_thresh,
-                                  self.area_thresh, hidden_dim=bank.hidden_dim, num_classes=K, use_dab=self.use_dab))
+            out.append(reportable(rows[slots[torch.argsort(ids[slots])]], K, ori_h, ori_w, *self._report_thresholds(b),
+                                  hidden_dim=bank.hidden_dim, num_classes=K, use_dab=self.use_dab))
         return out
 
     # ------------------------------------------------------------------ many sequences

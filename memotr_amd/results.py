@@ -346,6 +346,19 @@ class BankResultLog(_RowTable):
         bank_result_rows(bank, seq_frame, ori_wh, score_thresh, area_thresh, self.rows_f, self.rows_i, self.counters)
         self._bound += offered
 
+    @torch.no_grad()
+    def append_streams(self, bank, seq_frame: torch.Tensor, ori_wh: torch.Tensor, thresholds) -> None:
+        """``append`` with stream b filtered by setting b of ``thresholds`` (clip_ops.StreamThresholds): one launch of
+        ``clipops_bank_result_rows_streams_f32``.  In a threshold sweep every stream tracks the same sequence, and the
+        "sequence" column of ``seq_frame`` is the setting's index."""
+        from .functions.clip_ops import bank_result_rows_streams
+        if bank.ids.device != self.device:
+            raise ValueError(f"track bank on {bank.ids.device}, result log on {self.device}")
+        offered = bank.n_streams * bank.cap
+        self._make_room(offered)
+        bank_result_rows_streams(bank, seq_frame, ori_wh, thresholds, self.rows_f, self.rows_i, self.counters)
+        self._bound += offered
+
     @staticmethod
     def _as_rows(rows_i, rows_f) -> dict:
         out = {}
