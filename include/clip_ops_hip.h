@@ -480,6 +480,63 @@ int clipops_fill_gaps_f32(const float *rows_f, const int64_t *rows_i, const int3
                           int n_ids, int n_frames, int max_gap, int min_length, int32_t *workspace, float *out_f,
                           int64_t *out_i, int32_t *out_counters, int32_t *status, int capacity, void *stream);
 
+/* ---- error analysis: the match events of CLEAR, and the overlay's draw table coloured by event ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the bank entries: no entry point changed.)
+ * clipops_clear_events_f64 walks every sequence as CLEAR does (memotr_amd/evaluation.py: _clear_host; the same walk as
+ * trackeval_clear of include/track_eval_hip.h, which keeps only the counts) and keeps the decision of every row.  It
+ * works on the preprocessed, compacted arrays trackeval_clear is launched on, with the same meaning: sim float64, the
+ * similarity of every frame row-major (ground truth x tracker) behind sim_off int64 [F + 1]; gt_off / tr_off int32
+ * [F + 1]; gt_ids / tr_ids int32, relabelled 0 .. n - 1 per sequence; seq_off int32 [S + 1] in frames; n_gt_ids int32 [S];
+ * max_gt / max_tr the largest frame, max_gt_ids the largest n_gt_ids, each at most CLIPOPS_EVENTS_MAX_DIM.
+ *   frame     a frame without ground truth counts its tracker rows as false positives, one without tracker rows its
+ *             ground truth as misses, and neither touches the per-id state.  Otherwise the assignment maximises
+ *             1000 * [tracker id == the id's match in the previous evaluated frame] + similarity, entries with
+ *             similarity < 0.5 - eps set to 0; pairs are scipy.optimize.linear_sum_assignment's (assign_core.h) and a
+ *             pair counts when its similarity is at least 0.5 - eps.
+ *   output    gt_partner int32 [NG']: the matched tracker row's index within its frame, -1 for a miss; gt_flags int32
+ *             [NG']: bit 0 (CLIPOPS_EVENT_SWITCH) the id's last match ever was another tracker id, bit 1
+ *             (CLIPOPS_EVENT_FRAG) the id was matched before but not in the previous evaluated frame; tr_partner int32
+ *             [NT']: the matched ground-truth row's index within its frame, -1 for a false positive; counts int32
+ *             [S, 5] = CLR_TP, CLR_FN, CLR_FP, IDSW, Frag; status int32 [S]: 0, -1 no feasible assignment, -2 a frame
+ *             or an id count above what the launch was made for (the sequence's events are then all -1 / 0 and its
+ *             counts 0).  Every entry of the five arrays is written; the caller zeroes nothing.
+ * One wavefront per sequence; per ground-truth id the tracker id of its last match and the evaluated frame it happened
+ * in live in LDS (dynamic, above 64 KiB by opt-in).  Integer results only: the same inputs give the same bits.
+ * n_seqs == 0 launches nothing.  Arguments are checked on the host without touching a device: returns 1 for a negative
+ * size or a null pointer with n_seqs > 0, 2 for a size above CLIPOPS_EVENTS_MAX_DIM, 3 when the launch failed. */
+#define CLIPOPS_EVENTS_MAX_DIM 2048
+#define CLIPOPS_EVENT_SWITCH 1
+#define CLIPOPS_EVENT_FRAG 2
+int clipops_clear_events_f64(const double *sim, const int64_t *sim_off, const int32_t *gt_off, const int32_t *tr_off,
+                             const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *seq_off, int n_seqs,
+                             const int32_t *n_gt_ids, int max_gt, int max_tr, int max_gt_ids, int32_t *gt_partner,
+                             int32_t *gt_flags, int32_t *tr_partner, int32_t *counts, int32_t *status, void *stream);
+
+/* clipops_error_table_f64: the draw tables (include/track_draw_hip.h: 16 words a row) of all frames of a sequence in
+ * one launch, from the rows as the files give them: gt_boxes / tr_boxes float64 (n, 4) xywh, gt_off / tr_off int32
+ * [F + 1], gt_ids / tr_ids int32 (0 .. 2^31 - 1), gt_kind / tr_kind int32 the CLIPOPS_KIND_* of every row; table int32
+ * (F, max_rows, 16).
+ *   rows     of frame f: first its ground-truth rows of kind MISS in input order, labelled with the ground-truth id, then
+ *            its tracker rows of kind MATCH, SWITCH and FP in input order, labelled with the tracker id.  Any other kind
+ *            is not drawn.  A row that would land at or past max_rows is left out; every remaining row up to max_rows
+ *            is clipops_draw_table_f32's padding row (0, 0, -1, -1 and twelve zeros).
+ *   row      what render.track_table writes for that id and the box (x, y, x + w, y + h), each sum formed in float64
+ *            and rounded once to float32, with `width` the frame's width -- except the colour (word 4): MATCH
+ *            (0, 200, 0), FP (255, 0, 0), MISS (255, 200, 0), SWITCH (255, 0, 255) as r | g << 8 | b << 16, bytes 0 and
+ *            2 swapped for bgr, and the text colour (word 9), which follows from it by the same luma rule.
+ * One workgroup per frame, rows ranked by ballots.  n_frames * max_rows == 0 launches nothing.  Arguments are checked on
+ * the host without touching a device: returns 1 for a negative size, width or height below 1 or above 65535, font_scale
+ * outside 1 .. 64, more than 2^31 - 1 table rows or a null pointer; 3 when the launch failed. */
+#define CLIPOPS_KIND_IGNORED 0
+#define CLIPOPS_KIND_MATCH 1
+#define CLIPOPS_KIND_SWITCH 2
+#define CLIPOPS_KIND_MISS 3
+#define CLIPOPS_KIND_FP 4
+int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, const int32_t *gt_off, const int32_t *tr_off,
+                            const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *gt_kind, const int32_t *tr_kind,
+                            int n_frames, int max_rows, int width, int height, int bgr, int font_scale, int32_t *table,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ SYMBOLS = {
     "clipops_bank_result_rows_streams_f32": ([c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 7 + [c_int, c_void_p], c_int),
     "clipops_draw_table_f32": ([c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_float, c_float, c_int, c_int, c_void_p,
                                                                  c_void_p], c_int),
+    "clipops_clear_events_f64": ([c_void_p] * 7 + [c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 6, c_int),
+    "clipops_error_table_f64": ([c_void_p] * 8 + [c_int] * 6 + [c_void_p, c_void_p], c_int),
     "clipops_fill_gaps_workspace": ([c_int] * 3, c_long),
     "clipops_fill_gaps_f32": ([c_void_p] * 3 + [c_int] * 7 + [c_void_p] * 5 + [c_int, c_void_p], c_int),
 }

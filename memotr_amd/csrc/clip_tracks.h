@@ -1,6 +1,7 @@
 // clip_tracks.h -- the device side of the online tracker and of the submit path: result rows, the track bank, the
-// bank's result rows and the overlay's draw table.  One statement of the kept-track rule and of the counters' capacity
-// rule serves all of them (and clip_fill_gaps.h, included after this header).
+// bank's result rows, the overlay's draw table, and the error analysis (CLEAR's match events, the draw table coloured
+// by event).  One statement of the kept-track rule and of the counters' capacity rule serves the first four (and
+// clip_fill_gaps.h, included after this header); one statement of a draw-table row serves both tables.
 // Included by clip_ops.hip after clip_common.h.
 #pragma once
 
@@ -365,6 +366,37 @@ __device__ __forceinline__ int draw_table_palette(int i) {
 
 constexpr int DRAW_ROW_WORDS = 16;                  // TRACKDRAW_ROW_WORDS of include/track_draw_hip.h
 
+// One row as render.track_table writes it for `id` and the float32 xyxy box, in the colour rgb = r | g << 8 | b << 16
+// (bytes 0 and 2 swapped for bgr): the rounded corners, the tab above the box (inside it at the top edge, shifted left
+// at the right edge of a frame `width` wide), the text colour by the integer luma rule, the packed decimal digits.
+__device__ __forceinline__ void draw_table_row(int32_t *__restrict__ row, int id, float bx1, float by1, float bx2,
+                                               float by2, int rgb, int bgr, int font_scale, int width) {
+    const int x1 = draw_table_round(bx1), y1 = draw_table_round(by1);
+    const int r = rgb & 255, g = (rgb >> 8) & 255, bl = rgb >> 16;
+    int n_digits = 1;
+    for (int v = id; v >= 10; v /= 10) ++n_digits;
+    unsigned lo_word = 0, hi_word = 0;              // glyph k is the k-th digit from the left
+    for (int k = n_digits - 1, v = id; k >= 0; --k, v /= 10) {
+        const unsigned d = (unsigned)(v % 10);
+        if (k < 8) lo_word |= d << (4 * k);
+        else hi_word |= d << (4 * (k - 8));
+    }
+    const int tab_w = (6 * n_digits - 1) * font_scale + 2, tab_h = 7 * font_scale + 2;
+    const int ty1 = y1 - tab_h >= 0 ? y1 - tab_h : y1;
+    const int tx1 = min(x1, width - tab_w);
+    row[0] = x1, row[1] = y1, row[2] = draw_table_round(bx2), row[3] = draw_table_round(by2);
+    row[4] = bgr ? (bl | g << 8 | r << 16) : rgb;
+    row[5] = tx1, row[6] = ty1, row[7] = tx1 + tab_w - 1, row[8] = ty1 + tab_h - 1;
+    row[9] = ((77 * r + 150 * g + 29 * bl) >> 8) >= 128 ? 0 : 0xFFFFFF;
+    row[10] = n_digits, row[11] = (int32_t)lo_word, row[12] = (int32_t)hi_word;
+    row[13] = row[14] = row[15] = 0;
+}
+
+// the row that draws nothing: x2 < x1
+__device__ __forceinline__ void draw_table_padding(int32_t *__restrict__ row) {
+    for (int k = 0; k < DRAW_ROW_WORDS; ++k) row[k] = (k == 2 || k == 3) ? -1 : 0;
+}
+
 __global__ __launch_bounds__(BANK_THREADS) void draw_table_kernel(const float *__restrict__ boxes,
                                                                   const float *__restrict__ scores,
                                                                   const int64_t *__restrict__ ids, int cap, int K,
@@ -407,34 +439,200 @@ __global__ __launch_bounds__(BANK_THREADS) void draw_table_kernel(const float *_
             __syncthreads();                        // keys is written again by the next chunk
         }
         if (mine.key < 0) continue;
-        const int id = mine.key;
-        const int x1 = draw_table_round(mine.x1), y1 = draw_table_round(mine.y1);
-        const int rgb = draw_table_palette(id & 63);
-        const int r = rgb & 255, g = (rgb >> 8) & 255, bl = rgb >> 16;
-        int n_digits = 1;
-        for (int v = id; v >= 10; v /= 10) ++n_digits;
-        unsigned lo_word = 0, hi_word = 0;          // glyph k is the k-th digit from the left
-        for (int k = n_digits - 1, v = id; k >= 0; --k, v /= 10) {
-            const unsigned d = (unsigned)(v % 10);
-            if (k < 8) lo_word |= d << (4 * k);
-            else hi_word |= d << (4 * (k - 8));
-        }
-        const int tab_w = (6 * n_digits - 1) * font_scale + 2, tab_h = 7 * font_scale + 2;
-        const int ty1 = y1 - tab_h >= 0 ? y1 - tab_h : y1;
-        const int tx1 = min(x1, (int)ori_w - tab_w);
-        int32_t *row = rows + (long)rank * DRAW_ROW_WORDS;
-        row[0] = x1, row[1] = y1, row[2] = draw_table_round(mine.x2), row[3] = draw_table_round(mine.y2);
-        row[4] = bgr ? (bl | g << 8 | r << 16) : rgb;
-        row[5] = tx1, row[6] = ty1, row[7] = tx1 + tab_w - 1, row[8] = ty1 + tab_h - 1;
-        row[9] = ((77 * r + 150 * g + 29 * bl) >> 8) >= 128 ? 0 : 0xFFFFFF;
-        row[10] = n_digits, row[11] = (int32_t)lo_word, row[12] = (int32_t)hi_word;
-        row[13] = row[14] = row[15] = 0;
+        const int rgb = draw_table_palette(mine.key & 63);
+        draw_table_row(rows + (long)rank * DRAW_ROW_WORDS, mine.key, mine.x1, mine.y1, mine.x2, mine.y2, rgb, bgr,
+                       font_scale, (int)ori_w);
     }
     for (int p = total + tid; p < cap; p += BANK_THREADS) {      // the rows that draw nothing: x2 < x1
-        int32_t *row = rows + (long)p * DRAW_ROW_WORDS;
-        for (int k = 0; k < DRAW_ROW_WORDS; ++k) row[k] = (k == 2 || k == 3) ? -1 : 0;
+        draw_table_padding(rows + (long)p * DRAW_ROW_WORDS);
     }
 }
+
+// ---- error analysis (include/clip_ops_hip.h: clipops_clear_events_f64, clipops_error_table_f64) ----
+// CLEAR's walk a second time.  trackeval_clear (track_eval.hip) makes the same decisions and keeps their counts; that
+// library's entry points are fixed, so the walk that keeps the decisions is stated here, on the same assign_core.h.  It
+// needs less state: per ground-truth id the tracker id of its last match (`last`) and the evaluated frame that match
+// happened in (`last_at`).  "Matched in the previous evaluated frame" is last_at == step - 1, so nothing is reset per
+// frame; frames without ground truth or without tracker rows are not evaluated frames and do not advance `step`.
+constexpr double EVENTS_EPS = 0x1p-52;              // np.finfo('float').eps
+constexpr double EVENTS_THRESHOLD = 0.5;
+
+struct EventsView {
+    const double *s;
+    const int32_t *gid, *tid;       // the frame's ids
+    const int32_t *last, *last_at;  // [G]
+    int k, G, prev_step;
+    __device__ __forceinline__ double at(int i, int j) const {
+        const double v = s[(size_t)i * k + j];
+        if (v < EVENTS_THRESHOLD - EVENTS_EPS) return -0.0;
+        const int g = gid[i];
+        const bool kept = (unsigned)g < (unsigned)G && last_at[g] == prev_step && last[g] == tid[j];
+        return -((kept ? 1000.0 : 0.0) + v);
+    }
+};
+
+__host__ __device__ inline size_t events_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+// LDS of one sequence: the pair lists (2 * mn int32), last and last_at (2 * max_gt_ids int32), the solver's scratch
+__host__ inline size_t events_lds_bytes(int max_gt, int max_tr, int max_gt_ids) {
+    const int mn = max_gt < max_tr ? max_gt : max_tr, mx = max_gt < max_tr ? max_tr : max_gt;
+    return events_align16((size_t)2 * mn * 4) + events_align16((size_t)2 * max_gt_ids * 4) +
+           events_align16(assign::work_bytes(mn, mx));
+}
+
+__device__ __forceinline__ int wave_sum_i32(int x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// One wavefront per sequence.  A frame's rows are first written as unmatched by all lanes; behind the barriers of the
+// solver, lane p of the pair pass overwrites the two rows of pair p.  Ids are unique in a frame, so the pairs of a frame
+// touch different entries of last / last_at and the pass needs no order; the counts are lane sums, reduced at the end.
+__global__ __launch_bounds__(64) void clear_events_kernel(const double *__restrict__ sim,
+                                                           const int64_t *__restrict__ sim_off,
+                                                           const int32_t *__restrict__ gt_off,
+                                                           const int32_t *__restrict__ tr_off,
+                                                           const int32_t *__restrict__ gt_ids,
+                                                           const int32_t *__restrict__ tr_ids,
+                                                           const int32_t *__restrict__ seq_off,
+                                                           const int32_t *__restrict__ n_gt_ids, int max_gt, int max_tr,
+                                                           int max_gt_ids, int mn, int32_t *__restrict__ gt_partner,
+                                                           int32_t *__restrict__ gt_flags,
+                                                           int32_t *__restrict__ tr_partner,
+                                                           int32_t *__restrict__ counts, int32_t *__restrict__ status) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_events[];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int G = n_gt_ids[s];
+    int32_t *rows = reinterpret_cast<int32_t *>(s_events), *cols = rows + mn;
+    int32_t *last = reinterpret_cast<int32_t *>(s_events + events_align16((size_t)2 * mn * 4));
+    int32_t *last_at = last + max_gt_ids;
+    unsigned char *work = s_events + events_align16((size_t)2 * mn * 4) + events_align16((size_t)2 * max_gt_ids * 4);
+    const WaveLanes lanes{lane};
+    const int f_begin = seq_off[s], f_end = seq_off[s + 1];
+    int rc = (G < 0 || G > max_gt_ids) ? -2 : 0;
+    int n_tp = 0, n_fn = 0, n_fp = 0, n_idsw = 0, n_frag = 0;           // this lane's share
+    int step = 0;                                   // evaluated frames so far
+    if (rc == 0) {
+        lanes.each(G, [&](int i) { last[i] = -1; last_at[i] = -2; });
+        lanes.sync();
+    }
+    for (int f = f_begin; rc == 0 && f < f_end; ++f) {
+        const int g0 = gt_off[f], g = gt_off[f + 1] - g0, k0 = tr_off[f], k = tr_off[f + 1] - k0;
+        if (g < 0 || k < 0 || g > max_gt || k > max_tr) {
+            rc = -2;
+            break;
+        }
+        lanes.each(g, [&](int i) { gt_partner[g0 + i] = -1; gt_flags[g0 + i] = 0; });
+        lanes.each(k, [&](int j) { tr_partner[k0 + j] = -1; });
+        if (g == 0) {
+            if (lane == 0) n_fp += k;
+            continue;
+        }
+        if (k == 0) {
+            if (lane == 0) n_fn += g;
+            continue;
+        }
+        const int32_t *gid = gt_ids + g0, *tid = tr_ids + k0;
+        const double *sm = sim + sim_off[f];
+        const EventsView view{sm, gid, tid, last, last_at, k, G, step - 1};
+        const int n = assign::solve_view(lanes, view, g, k, work, rows, cols);
+        if (n < 0) {
+            rc = -1;
+            break;
+        }
+        lanes.sync();                               // the frame's unmatched rows are written; the pairs are visible
+        int n_match = 0;
+        lanes.each(n, [&](int p) {
+            const int i = rows[p], j = cols[p];
+            if (sm[(size_t)i * k + j] < EVENTS_THRESHOLD - EVENTS_EPS) return;      // (a kept score is >= 0.5 - eps > eps)
+            const int gi = gid[i], tj = tid[j];
+            if ((unsigned)gi >= (unsigned)G) return;
+            const int before = last[gi];
+            const bool sw = before >= 0 && before != tj;
+            const bool fr = before >= 0 && last_at[gi] != step - 1;
+            last[gi] = tj;
+            last_at[gi] = step;
+            gt_partner[g0 + i] = j;
+            gt_flags[g0 + i] = (sw ? CLIPOPS_EVENT_SWITCH : 0) | (fr ? CLIPOPS_EVENT_FRAG : 0);
+            tr_partner[k0 + j] = i;
+            n_idsw += sw, n_frag += fr, ++n_match;
+        });
+        n_tp += n_match;
+        n_fn -= n_match, n_fp -= n_match;           // (with lane 0's g and k below: g - matches, k - matches)
+        if (lane == 0) n_fn += g, n_fp += k;
+        ++step;
+        lanes.sync();                               // last / last_at are read by the next frame's solver
+    }
+    lanes.sync();
+    if (rc != 0) {                                  // nothing of a failed sequence is left half written
+        const int a0 = gt_off[f_begin], a1 = gt_off[f_end], b0 = tr_off[f_begin], b1 = tr_off[f_end];
+        lanes.each(a1 - a0, [&](int i) { gt_partner[a0 + i] = -1; gt_flags[a0 + i] = 0; });
+        lanes.each(b1 - b0, [&](int j) { tr_partner[b0 + j] = -1; });
+        n_tp = n_fn = n_fp = n_idsw = n_frag = 0;
+    }
+    n_tp = wave_sum_i32(n_tp), n_fn = wave_sum_i32(n_fn), n_fp = wave_sum_i32(n_fp);
+    n_idsw = wave_sum_i32(n_idsw), n_frag = wave_sum_i32(n_frag);
+    if (lane == 0) {
+        int32_t *o = counts + (size_t)s * 5;
+        o[0] = n_tp, o[1] = n_fn, o[2] = n_fp, o[3] = n_idsw, o[4] = n_frag;
+        status[s] = rc;
+    }
+}
+
+// r | g << 8 | b << 16 of an event kind; -1: the kind is not drawn
+__device__ __forceinline__ int error_table_colour(int kind) {
+    switch (kind) {
+        case CLIPOPS_KIND_MATCH: return 0 | 200 << 8 | 0 << 16;
+        case CLIPOPS_KIND_SWITCH: return 255 | 0 << 8 | 255 << 16;
+        case CLIPOPS_KIND_MISS: return 255 | 200 << 8 | 0 << 16;
+        case CLIPOPS_KIND_FP: return 255 | 0 << 8 | 0 << 16;
+        default: return -1;
+    }
+}
+
+// One workgroup per frame: the ground-truth rows, then the tracker rows, in chunks of 256; a drawn row's place is the
+// number of drawn rows before it (result_rows_kernel's ballot ranks, `base` running across chunks and sides).
+__global__ __launch_bounds__(256) void error_table_kernel(const double *__restrict__ gt_boxes,
+                                                          const double *__restrict__ tr_boxes,
+                                                          const int32_t *__restrict__ gt_off,
+                                                          const int32_t *__restrict__ tr_off,
+                                                          const int32_t *__restrict__ gt_ids,
+                                                          const int32_t *__restrict__ tr_ids,
+                                                          const int32_t *__restrict__ gt_kind,
+                                                          const int32_t *__restrict__ tr_kind, int max_rows, int width,
+                                                          int bgr, int font_scale, int32_t *__restrict__ table) {
+#pragma clang fp contract(off)
+    __shared__ int wave_total[4];
+    const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t *rows = table + (long)f * max_rows * DRAW_ROW_WORDS;
+    long base = 0;                                  // drawn rows before this chunk
+    for (int side = 0; side < 2; ++side) {
+        const double *boxes = side ? tr_boxes : gt_boxes;
+        const int32_t *ids = side ? tr_ids : gt_ids, *kinds = side ? tr_kind : gt_kind;
+        const int r0 = side ? tr_off[f] : gt_off[f], n = (side ? tr_off[f + 1] : gt_off[f + 1]) - r0;
+        for (int c0 = 0; c0 < n; c0 += 256) {       // (n is uniform: every thread makes every trip)
+            const int i = c0 + (int)threadIdx.x;
+            int kind = CLIPOPS_KIND_IGNORED, id = -1;
+            if (i < n) kind = kinds[r0 + i], id = ids[r0 + i];
+            const bool drawn = id >= 0 && (side ? (kind == CLIPOPS_KIND_MATCH || kind == CLIPOPS_KIND_SWITCH ||
+                                                   kind == CLIPOPS_KIND_FP)
+                                                : kind == CLIPOPS_KIND_MISS);
+            int before, total;
+            bank_ranks<4>(drawn, lane, wave, wave_total, before, total);
+            const long pos = base + before;
+            if (drawn && pos < max_rows) {
+                const double *b = boxes + (long)(r0 + i) * 4;
+                draw_table_row(rows + pos * DRAW_ROW_WORDS, id, (float)b[0], (float)b[1], (float)(b[0] + b[2]),
+                               (float)(b[1] + b[3]), error_table_colour(kind), bgr, font_scale, width);
+            }
+            base += total;
+            __syncthreads();                        // wave_total is written again by the next chunk
+        }
+    }
+    for (long p = base + threadIdx.x; p < max_rows; p += 256) draw_table_padding(rows + p * DRAW_ROW_WORDS);
+}
+
 // The argument checks the scalar and the per-stream entry points of the bank share, reported under the caller's name:
 // 1 = launch, 0 = nothing to do (ok() is set), -code = fail()'s code.
 int bank_update_args(const char *who, const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap,
@@ -547,5 +745,41 @@ int clipops_draw_table_f32(const float *boxes, const float *scores, const int64_
     if (!boxes || !scores || !ids || !ori_wh || !table) return fail(1, "clipops_draw_table_f32: null pointer");
     return launch("draw_table_kernel", draw_table_kernel, dim3(B), dim3(BANK_THREADS), 0, stream, boxes, scores, ids, cap,
                   K, ori_wh, score_thresh, area_thresh, bgr ? 1 : 0, font_scale, table) ? 3 : 0;
+}
+
+int clipops_clear_events_f64(const double *sim, const int64_t *sim_off, const int32_t *gt_off, const int32_t *tr_off,
+                             const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *seq_off, int n_seqs,
+                             const int32_t *n_gt_ids, int max_gt, int max_tr, int max_gt_ids, int32_t *gt_partner,
+                             int32_t *gt_flags, int32_t *tr_partner, int32_t *counts, int32_t *status, void *stream) {
+    const char *who = "clipops_clear_events_f64";
+    if (n_seqs < 0 || max_gt < 0 || max_tr < 0 || max_gt_ids < 0) return fail(1, who, "negative size");
+    if (max_gt > CLIPOPS_EVENTS_MAX_DIM || max_tr > CLIPOPS_EVENTS_MAX_DIM || max_gt_ids > CLIPOPS_EVENTS_MAX_DIM)
+        return fail(2, who, "a frame or an id count exceeds CLIPOPS_EVENTS_MAX_DIM = 2048");
+    if (n_seqs == 0) return ok();
+    if (!sim || !sim_off || !gt_off || !tr_off || !gt_ids || !tr_ids || !seq_off || !n_gt_ids || !gt_partner ||
+        !gt_flags || !tr_partner || !counts || !status)
+        return fail(1, who, "null pointer");
+    static std::atomic<unsigned long long> allowed{0};
+    const size_t lds = events_lds_bytes(max_gt, max_tr, max_gt_ids);    // (at most 126 KiB at the largest sizes)
+    if (allow_lds(reinterpret_cast<const void *>(clear_events_kernel), lds, allowed)) return 3;
+    return launch("clear_events_kernel", clear_events_kernel, dim3(n_seqs), dim3(64), lds, stream, sim, sim_off, gt_off,
+                  tr_off, gt_ids, tr_ids, seq_off, n_gt_ids, max_gt, max_tr, max_gt_ids,
+                  max_gt < max_tr ? max_gt : max_tr, gt_partner, gt_flags, tr_partner, counts, status) ? 3 : 0;
+}
+
+int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, const int32_t *gt_off, const int32_t *tr_off,
+                            const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *gt_kind, const int32_t *tr_kind,
+                            int n_frames, int max_rows, int width, int height, int bgr, int font_scale, int32_t *table,
+                            void *stream) {
+    const char *who = "clipops_error_table_f64";
+    if (n_frames < 0 || max_rows < 0) return fail(1, who, "negative size");
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(1, who, "width or height outside 1 .. 65535");
+    if (font_scale < 1 || font_scale > 64) return fail(1, who, "font_scale outside 1 .. 64");
+    if ((long)n_frames * max_rows > 0x7fffffffL) return fail(1, who, "more than 2^31 - 1 table rows");
+    if ((long)n_frames * max_rows == 0) return ok();
+    if (!gt_boxes || !tr_boxes || !gt_off || !tr_off || !gt_ids || !tr_ids || !gt_kind || !tr_kind || !table)
+        return fail(1, who, "null pointer");
+    return launch("error_table_kernel", error_table_kernel, dim3(n_frames), dim3(256), 0, stream, gt_boxes, tr_boxes,
+                  gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind, max_rows, width, bgr ? 1 : 0, font_scale, table) ? 3 : 0;
 }
 }  // extern "C"

@@ -642,6 +642,11 @@ class TrackingEvaluator:
     def evaluate(self) -> Dict[str, dict]:
         return evaluate_sequences(self.sequences(), self.benchmark, device=self.device if self.device else "cpu")
 
+    def events(self) -> Dict[str, object]:
+        """``{name: diagnose.SequenceEvents}`` of what was collected: the decisions behind CLEAR's counts, per row."""
+        from .diagnose import clear_events
+        return clear_events(pack_sequences(self.sequences()), self.benchmark, device=self.device)
+
 
 # ------------------------------------------------------------------------------------------------------ text files
 def read_mot_txt(path: str) -> np.ndarray:
@@ -665,8 +670,8 @@ def _rows_by_frame(rows: np.ndarray):
     return {int(f): rows[frames == f] for f in np.unique(frames)}
 
 
-def evaluate_files(gt_root: str, tracker_dir: str, seqmap: str, benchmark: str = "MOT17", device=None) -> Dict[str, dict]:
-    """Score result files in the layout ``eval_engine.py`` hands to TrackEval: ground truth in
+def load_files(gt_root: str, tracker_dir: str, seqmap: str, benchmark: str = "MOT17", device=None) -> TrackingEvaluator:
+    """A ``TrackingEvaluator`` holding result files in the layout ``eval_engine.py`` hands to TrackEval: ground truth in
     ``<gt_root>/<seq>/gt/gt.txt`` (length from ``<gt_root>/<seq>/seqinfo.ini`` where it exists), results in
     ``<tracker_dir>/<seq>.txt``, sequence names in ``seqmap`` (one per line under a ``name`` header)."""
     with open(seqmap) as f:
@@ -685,7 +690,12 @@ def evaluate_files(gt_root: str, tracker_dir: str, seqmap: str, benchmark: str =
         for f, r in _rows_by_frame(tr).items():
             ev.add_tracker_rows(seq, f, r[:, 1].astype(np.int64), r[:, 2:6])
         ev._gt.setdefault(seq, {})
-    return ev.evaluate()
+    return ev
+
+
+def evaluate_files(gt_root: str, tracker_dir: str, seqmap: str, benchmark: str = "MOT17", device=None) -> Dict[str, dict]:
+    """Score the result files ``load_files`` reads."""
+    return load_files(gt_root, tracker_dir, seqmap, benchmark, device).evaluate()
 
 
 def _seq_length(ini_path: str) -> Optional[int]:
