@@ -77,7 +77,8 @@ extern "C" {
 #define MSDA_ERANGE (-2)   /* a tensor is too large for 32-bit index arithmetic   */
 #define MSDA_ENOTSUP (-3)  /* dtype/shape combination not supported (bf16: D%8)   */
 
-/* ABI version: bumped on any signature change. */
+/* ABI version: bumped on any signature change (8: the attention-map entry points). */
+#define MSDA_ABI_VERSION 8
 int msda_abi_version(void);
 
 /* Thread-local, never NULL; empty string when the last call succeeded. */
@@ -304,6 +305,60 @@ int msda_sample_indices_f32(const int64_t *shapes_dev, const float *loc,
 int msda_fused_points_f32(const int64_t *shapes_dev, const float *proj, int proj_stride, const float *ref,
                           int ref_dim, int N, int M, int L, int Lq, int P,
                           float *loc_out, float *attn_out, void *stream);
+
+/* ---- attention maps (ABI 8; memotr_amd/csrc/msda_attn_map.h) ----
+ * Where the decoder queries of a track sample, as a picture.  Both steps are defined by the numpy statements of
+ * memotr_amd/attention_maps.py (attention_heat_host, blend_heat_host) and equal them bit for bit: everything past the
+ * first float32 multiply is integer arithmetic, and integer sums do not depend on their order.
+ *
+ * Heat.  For every entry k of rows / planes (int32 [K], device), every layer of the launch and every point (m, l, j) of
+ * query row q = rows[k] of batch item 0 (the entry is skipped for a layer when q < 0, q >= Lq of that layer, or
+ * planes[k] is outside 0 .. n_planes - 1):
+ *     x = loc_x * sx, y = loc_y * sy                        one float32 product each
+ *     dropped unless -(r+1) <= x < wc + r + 1 and -(r+1) <= y < hc + r + 1   (NaN and +-inf drop here)
+ *     ix = floor(x), iy = floor(y)
+ *     wq = attn > 0 ? rint(min(attn, 1) * 4096) : 0         ties to even
+ *     heat[planes[k], iy + dy, ix + dx] += wq * stamp[dy + r, dx + r]      for the stamp cells inside the plane
+ * `stamp` is a device table of (2r+1)^2 uint16, r = radius <= 8; `heat` (n_planes, hc, wc) uint64 is overwritten, or
+ * added to when `accumulate` != 0; `peak` (n_planes) uint64 receives max(heat[p]) of the result either way.
+ * A launch takes 1 .. 8 layers, each with its own query count:
+ *     msda_attention_heat_points_f32   a = loc (Lq, M, L, P, 2), b = attn (Lq, M, L, P); proj_stride / ref_dim unused
+ *     msda_attention_heat_f32          a = proj (Lq, proj_stride), b = ref (Lq, L, ref_dim): the points are formed in the
+ *                                      kernel exactly as msda_fused_points_f32 writes them and never reach memory
+ *                                      (L * P <= 64, else MSDA_ENOTSUP; `shapes_dev` as for the fused prologue)
+ * `layers` is HOST memory, read before the call returns.
+ *
+ * Blend.  msda_attention_blend_u8 blends 1 .. 16 planes, in order, into a (H, W, 3) uint8 frame with explicit row
+ * pitches in bytes (dst may be src); heat is (n_planes, ceil(H / cell), ceil(W / cell)), lut (n_planes, 256, 3) uint8:
+ *     s = full_scale ? full_scale : peak[p];  level = s == 0 ? 0 : min(255, (heat * 255 + s / 2) / s)
+ *     a = (level * max_alpha + 127) / 255;  where a > 0:  px[c] = (lut[p, level, c] * a + px[c] * (255 - a) + 127) / 255
+ * Only the 3 * W bytes of a row are written.
+ * All three validate their arguments on the host (no device needed for an argument error), enqueue on `stream`, allocate
+ * nothing and never synchronise. */
+typedef struct msda_heat_layer {
+    const float *a;
+    const float *b;
+    int Lq;
+    int proj_stride;
+    int ref_dim;
+    int reserved;
+} msda_heat_layer;
+
+int msda_attention_heat_points_f32(const msda_heat_layer *layers, int n_layers, int M, int L, int P,
+                                   const int32_t *rows, const int32_t *planes, int K,
+                                   const uint16_t *stamp, int radius, float sx, float sy,
+                                   uint64_t *heat, uint64_t *peak, int n_planes, int hc, int wc,
+                                   int accumulate, void *stream);
+
+int msda_attention_heat_f32(const int64_t *shapes_dev, const msda_heat_layer *layers, int n_layers, int M, int L, int P,
+                            const int32_t *rows, const int32_t *planes, int K,
+                            const uint16_t *stamp, int radius, float sx, float sy,
+                            uint64_t *heat, uint64_t *peak, int n_planes, int hc, int wc,
+                            int accumulate, void *stream);
+
+int msda_attention_blend_u8(const uint8_t *src, long src_pitch, uint8_t *dst, long dst_pitch, int W, int H,
+                            const uint64_t *heat, const uint64_t *peak, const uint8_t *lut, int n_planes,
+                            int cell, int max_alpha, uint64_t full_scale, void *stream);
 
 /* ---- tuning knobs (benchmarks / tests only; defaults pick the fastest correct path) ----
  * key: "fwd_variant" (0 = auto, 1 = generic one-thread-per-output kernel, 3 = D = 32 gather, 12 = windowed forward) |

@@ -12,7 +12,7 @@ from . import _cabi
 
 LIB_PATH = os.environ.get("MEMOTR_MSDA_LIB") or _cabi.lib_path("libmsda_hip.so")   # (override: A/B builds)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 c_int = ctypes.c_int
 c_void_p = ctypes.c_void_p
@@ -29,8 +29,24 @@ _BWD_WS_ARGS = _BWD_ARGS[:-1] + [c_void_p, ctypes.c_size_t, c_void_p]
 # ... + fwd_out after grad_out
 _FUSED_BWD_OUT_ARGS = _FUSED_BWD_WS_ARGS[:9] + [c_void_p] + _FUSED_BWD_WS_ARGS[9:]
 
+
+class HeatLayer(ctypes.Structure):
+    """``msda_heat_layer``: one decoder layer of an attention-heat launch (include/msda_hip.h)."""
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("Lq", c_int), ("proj_stride", c_int), ("ref_dim", c_int),
+                ("reserved", c_int)]
+
+
+# attention maps: layers, n_layers, M, L, P, rows, planes, K, stamp, radius, sx, sy, heat, peak, n_planes, hc, wc,
+# accumulate, stream
+_HEAT_ARGS = ([ctypes.POINTER(HeatLayer)] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_float,
+              ctypes.c_float, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p])
+
 SYMBOLS = {
     "msda_abi_version": ([], c_int),
+    "msda_attention_heat_points_f32": (_HEAT_ARGS, c_int),
+    "msda_attention_heat_f32": ([c_void_p] + _HEAT_ARGS, c_int),
+    "msda_attention_blend_u8": ([c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_int, c_int, ctypes.c_uint64, c_void_p], c_int),
     "msda_last_error": ([], ctypes.c_char_p),
     "msda_last_kernel": ([], ctypes.c_char_p),
     "msda_forward_f32": (_FWD_ARGS, c_int),

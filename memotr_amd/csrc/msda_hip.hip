@@ -79,6 +79,7 @@ __device__ __forceinline__ double t_exp(double x) { return exp(x); }
 #include "msda_bwd_rows.h"
 #include "msda_bwd_bins.h"
 #include "msda_bwd_sorted.h"
+#include "msda_attn_map.h"
 
 // ----------------------------------------------------------------------------------------
 // host side
@@ -717,7 +718,7 @@ FusedArgs fused_args(const float *proj, int proj_stride, const float *ref, int r
 
 extern "C" {
 
-int msda_abi_version(void) { return 7; }
+int msda_abi_version(void) { return MSDA_ABI_VERSION; }
 
 void msda_set_call_site(uint64_t site) { g_site = site; }
 
@@ -934,6 +935,87 @@ int msda_fused_points_f32(const int64_t *shapes_dev, const float *proj, int proj
     hipLaunchKernelGGL(msda_fused_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, shapes_dev, src, n_rows,
                        M, L, P, loc_out, attn_out);
     return check_launch("msda_fused_points_kernel");
+}
+
+// ---- attention maps (ABI 8; memotr_amd/csrc/msda_attn_map.h) ----
+static int attention_heat(bool fused, const int64_t *shapes_dev, const msda_heat_layer *layers, int n_layers, int M,
+                          int L, int P, const int32_t *rows, const int32_t *planes, int K, const uint16_t *stamp,
+                          int radius, float sx, float sy, uint64_t *heat, uint64_t *peak, int n_planes, int hc, int wc,
+                          int accumulate, void *stream) {
+    if (!layers || !stamp || !heat || !peak || (fused && !shapes_dev)) return fail(MSDA_EINVAL, "null pointer argument");
+    if (K < 0 || (K > 0 && (!rows || !planes))) return fail(MSDA_EINVAL, "null row / plane table");
+    if (n_layers < 1 || n_layers > kHeatMaxLayers) return fail(MSDA_EINVAL, "1 to 8 layers per launch");
+    if (radius < 0 || radius > kHeatMaxRadius) return fail(MSDA_EINVAL, "stamp radius is 0 to 8");
+    if (M <= 0 || L <= 0 || P <= 0 || n_planes <= 0 || hc <= 0 || wc <= 0) return fail(MSDA_EINVAL, "non-positive dimension");
+    if (n_planes > 65535) return fail(MSDA_EINVAL, "at most 65535 heat planes");
+    if ((double)n_planes * hc * wc > 2147483647.0 || (double)K * n_layers * M > 2147483647.0)
+        return fail(MSDA_ERANGE, "heat planes / row table exceed 2^31 elements");
+    if (fused && L * P > kMaxFusedLP) return fail(MSDA_ENOTSUP, "fused prologue supports at most 64 sampling points per head");
+    HeatLayers ly;
+    memset(&ly, 0, sizeof(ly));
+    ly.n = n_layers;
+    for (int i = 0; i < n_layers; ++i) {
+        const msda_heat_layer &d = layers[i];
+        if (!d.a || !d.b) return fail(MSDA_EINVAL, "null layer pointer");
+        if (d.Lq < 0) return fail(MSDA_EINVAL, "negative query count");
+        if (fused && d.ref_dim != 2 && d.ref_dim != 4) return fail(MSDA_EINVAL, "reference points must have 2 or 4 coordinates");
+        if (fused && d.proj_stride < 3 * M * L * P) return fail(MSDA_EINVAL, "projection rows shorter than 3*M*L*P");
+        if ((double)d.Lq * (fused ? (double)d.proj_stride : 2.0 * M * L * P) > 2147483647.0)
+            return fail(MSDA_ERANGE, "tensor exceeds 2^31 elements");
+        ly.a[i] = d.a; ly.b[i] = d.b; ly.Lq[i] = d.Lq; ly.proj_stride[i] = d.proj_stride; ly.ref_dim[i] = d.ref_dim;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(peak, 0, sizeof(uint64_t) * (size_t)n_planes, st);    // (the kernel takes maxima into it)
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "hipMemsetAsync(peak): %s", hipGetErrorString(e));
+        return (int)e;
+    }
+    const int tiles = ((wc + kHeatTile - 1) / kHeatTile) * ((hc + kHeatTile - 1) / kHeatTile);
+    const int threads = heat_threads(((long)K * n_layers * M + n_planes - 1) / n_planes);     // (rows spread evenly: a guess)
+    auto *h = reinterpret_cast<unsigned long long *>(heat);
+    auto *pk = reinterpret_cast<unsigned long long *>(peak);
+    if (fused)
+        hipLaunchKernelGGL(msda_attn_heat_kernel<true>, dim3(tiles, n_planes), dim3(threads), 0, st, ly, shapes_dev, M, L, P,
+                           rows, planes, K, stamp, radius, sx, sy, h, pk, n_planes, hc, wc, accumulate);
+    else
+        hipLaunchKernelGGL(msda_attn_heat_kernel<false>, dim3(tiles, n_planes), dim3(threads), 0, st, ly, shapes_dev, M, L,
+                           P, rows, planes, K, stamp, radius, sx, sy, h, pk, n_planes, hc, wc, accumulate);
+    return check_launch("msda_attn_heat_kernel");
+}
+
+int msda_attention_heat_points_f32(const msda_heat_layer *layers, int n_layers, int M, int L, int P,
+                                   const int32_t *rows, const int32_t *planes, int K, const uint16_t *stamp, int radius,
+                                   float sx, float sy, uint64_t *heat, uint64_t *peak, int n_planes, int hc, int wc,
+                                   int accumulate, void *stream) {
+    return attention_heat(false, nullptr, layers, n_layers, M, L, P, rows, planes, K, stamp, radius, sx, sy, heat, peak,
+                          n_planes, hc, wc, accumulate, stream);
+}
+
+int msda_attention_heat_f32(const int64_t *shapes_dev, const msda_heat_layer *layers, int n_layers, int M, int L, int P,
+                            const int32_t *rows, const int32_t *planes, int K, const uint16_t *stamp, int radius,
+                            float sx, float sy, uint64_t *heat, uint64_t *peak, int n_planes, int hc, int wc,
+                            int accumulate, void *stream) {
+    return attention_heat(true, shapes_dev, layers, n_layers, M, L, P, rows, planes, K, stamp, radius, sx, sy, heat, peak,
+                          n_planes, hc, wc, accumulate, stream);
+}
+
+int msda_attention_blend_u8(const uint8_t *src, long src_pitch, uint8_t *dst, long dst_pitch, int W, int H,
+                            const uint64_t *heat, const uint64_t *peak, const uint8_t *lut, int n_planes, int cell,
+                            int max_alpha, uint64_t full_scale, void *stream) {
+    if (!src || !dst || !heat || !peak || !lut) return fail(MSDA_EINVAL, "null pointer argument");
+    if (W <= 0 || H <= 0) return fail(MSDA_EINVAL, "non-positive frame size");
+    if (cell < 1) return fail(MSDA_EINVAL, "cell size is at least 1 pixel");
+    if (n_planes < 1 || n_planes > kBlendMaxPlanes) return fail(MSDA_EINVAL, "1 to 16 planes per launch");
+    if (max_alpha < 0 || max_alpha > 255) return fail(MSDA_EINVAL, "max_alpha is 0 to 255");
+    if (src_pitch < 3L * W || dst_pitch < 3L * W) return fail(MSDA_EINVAL, "row pitch shorter than 3 * W bytes");
+    if ((H + kBlendTileH - 1) / kBlendTileH > 65535) return fail(MSDA_ERANGE, "frame too tall");
+    const int hc = (H + cell - 1) / cell, wc = (W + cell - 1) / cell;
+    hipLaunchKernelGGL(msda_attn_blend_kernel, dim3((W + kBlendTileW - 1) / kBlendTileW, (H + kBlendTileH - 1) / kBlendTileH),
+                       dim3(256), 0, (hipStream_t)stream, src, src_pitch, dst, dst_pitch, W, H,
+                       reinterpret_cast<const unsigned long long *>(heat),
+                       reinterpret_cast<const unsigned long long *>(peak), lut, n_planes, hc, wc, cell, max_alpha,
+                       (unsigned long long)full_scale);
+    return check_launch("msda_attn_blend_kernel");
 }
 
 int msda_sample_indices_f32(const int64_t *shapes_dev, const float *loc, int N, int M, int L, int Lq, int P,

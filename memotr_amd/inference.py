@@ -283,6 +283,57 @@ class SequenceTracker:
             writer.add(idx, cur, result, bgr=bgr)
             yield idx, result
 
+    def track_attention(self, source, writer, *, ids=None, layers=None, bgr: bool = False):
+        """``track_annotated`` with the attention maps of the tracks under the boxes (attention_maps.py): ``writer`` is
+        an ``attention_maps.AttentionWriter``; yields exactly what ``track_annotated`` yields.  ``ids=[...]`` (at most
+        16): plane k is the map of track ``ids[k]``, tinted with ``render.palette_entry(id)`` -- the colour is constant,
+        the alpha follows the level; ``ids=None``: one plane holding every live track that entered the frame plus the
+        newborn, with ``HEAT_LUT``.  ``layers``: the decoder layers that count (default: all).
+        The decoder runs under an ``AttentionTap`` (``self.attention_tap`` while the generator is alive), i.e. eagerly:
+        the results are those of ``MEMOTR_INFER_GRAPHS=0``.  The row table of a frame is built on the device from the
+        ids that entered it and the runtime tracker's newborn rows; nothing is read back per frame beyond
+        ``step_raw``'s own report."""
+        from . import attention_maps as A
+        from .data.frames import padded_size
+        from .render import palette_entry
+        if ids is not None:
+            ids = [int(i) for i in ids]
+            if not 1 <= len(ids) <= A.MAX_PLANES:
+                raise ValueError(f"ids: 1 .. {A.MAX_PLANES} track ids")
+        n_planes = 1 if ids is None else len(ids)
+        lut = None if ids is None else A.constant_lut([palette_entry(i) for i in ids])
+        want = None if ids is None else torch.as_tensor(ids, dtype=torch.long).to(self.device)
+        n_det = self.core.n_det_queries
+        tap = A.AttentionTap(self.model)
+        n_layers = len(tap.decoder.layers)
+        layers = list(range(n_layers)) if layers is None else [int(lid) for lid in layers]
+        if not layers or any(not 0 <= lid < n_layers for lid in layers):
+            raise ValueError(f"layers: decoder layers 0 .. {n_layers - 1}")
+        heat = peak = None
+        with torch.no_grad():
+            tap.__enter__()
+        self.attention_tap = tap
+        try:
+            for idx, cur, nxt in self._frames(source, bgr, on_device=True):
+                ids_before = self.tracks[0].ids
+                result = self.step_raw(cur, nxt, bgr=bgr)
+                ori_h, ori_w = int(cur.shape[0]), int(cur.shape[1])
+                th, tw = target_size(ori_h, ori_w, *self.raw_size)
+                Hp, Wp = padded_size(th, tw)
+                hc, wc = -(-ori_h // writer.cell), -(-ori_w // writer.cell)
+                rows, planes = A.frame_rows(ids_before, self.tracker.last_newborn_rows,
+                                            self.tracker.last_newborn_first_id, n_det, want)
+                if heat is not None and tuple(heat.shape) != (n_planes, hc, wc):
+                    heat = peak = None
+                heat, peak = A.tap_heat(tap, layers, rows, planes, n_planes, hc, wc,
+                                        A.heat_scale(Wp, ori_w, tw, writer.cell), A.heat_scale(Hp, ori_h, th, writer.cell),
+                                        writer.stamp, heat=heat, peak=peak)
+                writer.add_attention(idx, cur, result, heat, peak, lut, bgr=bgr)
+                yield idx, result
+        finally:
+            tap.__exit__(None, None, None)
+            self.attention_tap = None
+
     def track_logged(self, source, log, *, bgr: bool = False) -> int:
         """``track`` / ``track_jpeg`` (``source`` as for ``track_annotated``) with the reportable rows of every frame
         appended to ``log`` (results.ResultLog) on the device instead of being brought to the host: one launch per frame

@@ -41,6 +41,7 @@ class DeformableDecoder(nn.Module):
         state = self.__dict__.copy()
         state.pop("_decoder_graphs", None)        # captured hipGraphs are per-process objects: never pickled / deep-copied
         state.pop("_infer_graphs", None)
+        state.pop("_attention_tap", None)         # an active attention_maps.AttentionTap belongs to its with-block
         return state
 
     def graphs(self) -> DecoderGraphs:
@@ -101,15 +102,17 @@ class DeformableDecoder(nn.Module):
         parameters their graphs read."""
         if not self.return_intermediate:
             raise NotImplementedError("Not Support for no Inter Outputs.")
-        if (frame_slot is not None and reference_points.shape[-1] == 4 and src_padding_mask is not None
+        # an active attention_maps.AttentionTap: the eager loop below, where the tap sees every layer's inputs
+        tap = self.__dict__.get("_attention_tap")
+        if (tap is None and frame_slot is not None and reference_points.shape[-1] == 4 and src_padding_mask is not None
                 and self.graphs().usable(tgt, src)):
             res = self._forward_graphed(tgt, reference_points, src, src_spatial_shapes, src_level_start_index,
                                         src_valid_ratios, query_pos, query_mask, src_padding_mask, frame_slot,
                                         clip_key)
             if res is not None:
                 return res
-        if (not torch.is_grad_enabled() and reference_points.shape[-1] == 4 and src_padding_mask is not None
-                and self.infer_graphs().decode_usable(self, tgt, src)):
+        if (tap is None and not torch.is_grad_enabled() and reference_points.shape[-1] == 4
+                and src_padding_mask is not None and self.infer_graphs().decode_usable(self, tgt, src)):
             res = self._forward_graphed(tgt, reference_points, src, src_spatial_shapes, src_level_start_index,
                                         src_valid_ratios, query_pos, query_mask, src_padding_mask, None,
                                         infer=True)
@@ -139,6 +142,8 @@ class DeformableDecoder(nn.Module):
                 query_pos = raw_pos if lid == 0 else self.query_scale(output) * raw_pos
             layer_inputs.append(output)
             merge = lid >= self.merge_det_track_layer
+            if tap is not None:
+                tap.record_reference(lid, reference_points)
             if self.use_checkpoint:
                 output = checkpoint(layer, output, query_pos, ref_in, src, src_spatial_shapes, src_level_start_index,
                                     query_mask, src_padding_mask, merge, use_reentrant=False)

@@ -32,6 +32,10 @@ class RuntimeTracker:
             MotionState(motion_max_length, motion_min_length, "cpu", capacity=1)     # (argument errors: raised here)
         self.visualize = visualize
         self.use_dab = use_dab
+        # the last update's newborn: their detect-query rows (device) and the id of the first one.  With the ids that
+        # entered the frame this names the (query row, track id) pairs of a frame (attention_maps.py).
+        self.last_newborn_rows = None
+        self.last_newborn_first_id = 0
 
     def update(self, model_outputs: dict, tracks: List[TrackInstances]):
         assert len(tracks) == 1
@@ -64,6 +68,7 @@ class RuntimeTracker:
         # (seven of them were most of an inference frame's host time, tools/infer_gaps.py)
         keep = torch.max(scores_all[0][:n_dets], dim=-1).values >= self.det_score_thresh
         idx = keep.nonzero().squeeze(1)
+        self.last_newborn_rows, self.last_newborn_first_id = idx, self.max_obj_id
         pick = lambda x: x[0][:n_dets].index_select(0, idx)  # noqa: E731
         new = TrackInstances(hidden_dim=t.hidden_dim, num_classes=t.num_classes)
         new.logits = pick(model_outputs["pred_logits"])
