@@ -537,6 +537,68 @@ int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, cons
                             int n_frames, int max_rows, int width, int height, int bgr, int font_scale, int32_t *table,
                             void *stream);
 
+/* ---- association analysis: HOTA's and Identity's matches kept, reduced per identity, drawn as a timeline ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the error-analysis entries: no entry point changed.)
+ * The four entries work on the preprocessed, compacted arrays and the per-sequence tables of include/track_eval_hip.h
+ * (trackeval_accumulate's outputs: alignment float64 and id_matches int32 behind cell_off int64 [S + 1], gt_count /
+ * tr_count int32 behind gid_off / tid_off int32 [S + 1]; n_gt_ids / n_tr_ids int32 [S] = G, K of a sequence).  All of
+ * them check their arguments on the host without touching a device: 1 for a negative size, an index out of range or a
+ * null pointer, 2 for a size above its limit, 3 when the launch failed.
+ *
+ * clipops_hota_events_f64: one wavefront per frame (frame_seq int32 [F]: the frame's sequence) solves
+ * linear_sum_assignment(-(alignment[gt id, tracker id] * sim)) as trackeval_hota_match does (assign_core.h) and keeps the
+ * pairs.  `level` of a pair is the number of thresholds a with sim >= alphas[a] - eps (alphas: CLIPOPS_ASSOC_ALPHAS
+ * ascending float64 in host memory, read during the call), so the pair is a true positive at threshold a exactly when
+ * a < level.  gt_partner / tr_partner int32 [NG'] / [NT']: the partner row's index within its frame, -1; gt_level /
+ * tr_level int32: the pair's level, 0.  A pair of level 0 is reported as no pair.  status int32 [F]: 0, -1 no feasible
+ * assignment, -2 a frame above max_gt / max_tr (the frame's rows are then all -1 / 0).  Every entry of the five arrays is
+ * written.  matches int32 [19 * cells], or null: behind 19 * cell_off[s], [a][gt id][tracker id] is incremented for every
+ * pair and every a < level -- trackeval_hota_match's table; the caller zeroes it.  max_gt / max_tr at most
+ * CLIPOPS_EVENTS_MAX_DIM.  n_frames == 0 launches nothing. */
+#define CLIPOPS_ASSOC_ALPHAS 19
+int clipops_hota_events_f64(const double *sim, const int64_t *sim_off, const int32_t *gt_off, const int32_t *tr_off,
+                            const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *frame_seq, int n_frames,
+                            const int32_t *n_tr_ids, const int64_t *cell_off, const double *alignment,
+                            const double *alphas, int max_gt, int max_tr, int32_t *gt_partner, int32_t *gt_level,
+                            int32_t *tr_partner, int32_t *tr_level, int32_t *matches, int32_t *status, void *stream);
+
+/* clipops_identity_pairs_i32: one wavefront per sequence solves the Identity metric's (G + K) x (G + K) problem
+ * (memotr_amd/evaluation.py: _identity_host; the cost is a function of gt_count, tr_count and id_matches, never a
+ * matrix) as trackeval_identity does and keeps the map: gt_id_partner int32 [sum G] the tracker id a ground-truth id is
+ * credited to, -1; gt_idtp int32 its id_matches entry, 0; tr_id_partner / tr_idtp int32 [sum K] the same pairs read from
+ * the tracker side.  status int32 [S]: 0, -1, -2 for G + K above max_ids (at most CLIPOPS_EVENTS_MAX_DIM); the
+ * sequence's ids are then all -1 / 0.  Every entry is written.  n_seqs == 0 launches nothing. */
+int clipops_identity_pairs_i32(int n_seqs, const int32_t *n_gt_ids, const int32_t *n_tr_ids, const int64_t *cell_off,
+                               const int32_t *gid_off, const int32_t *tid_off, const int32_t *gt_count,
+                               const int32_t *tr_count, const int32_t *id_matches, int max_ids, int32_t *gt_id_partner,
+                               int32_t *gt_idtp, int32_t *tr_id_partner, int32_t *tr_idtp, int32_t *status,
+                               void *stream);
+
+/* clipops_assoc_reduce_f64: HOTA's association sums per identity, one wavefront per (id, sequence, side), from
+ * matches (m = matches[a][g][k]), gt_count (gc) and tr_count (tc).  For a ground-truth id g: gt_tp int32 [sum G, 19] =
+ * sum_k m; gt_num float64 [sum G, 2, 19] = sum_k m * (m / max(1, gc[g] + tc[k] - m)) and sum_k m * (m / max(1, gc[g]));
+ * gt_top int32 [sum G, 3] at threshold alpha_index: the number of k with m > 0, the k of the largest m (ties: the lowest
+ * k; -1 without any) and that m.  For a tracker id k the mirror image over g, with max(1, tc[k]) in the second sum.
+ * Every product and quotient is rounded once (no contraction); a lane adds its terms in ascending id order and the 64
+ * partial sums meet in a fixed xor tree, so the same inputs give the same bits.  max_side_ids: the largest G or K, at most
+ * CLIPOPS_EVENTS_MAX_DIM; at most 65535 sequences.  Every entry is written.  n_seqs * max_side_ids == 0 launches nothing. */
+int clipops_assoc_reduce_f64(int n_seqs, const int32_t *n_gt_ids, const int32_t *n_tr_ids, const int64_t *cell_off,
+                             const int32_t *gid_off, const int32_t *tid_off, const int32_t *gt_count,
+                             const int32_t *tr_count, const int32_t *matches, int max_side_ids, int alpha_index,
+                             int32_t *gt_tp, double *gt_num, int32_t *gt_top, int32_t *tr_tp, double *tr_num,
+                             int32_t *tr_top, void *stream);
+
+/* clipops_timeline_u8: the identity timeline of one sequence, image uint8 (n_ids * cell_h, n_frames * cell_w, 3): one row
+ * of cells per ground-truth identity, one column per frame.  gt_off int32 [F + 1] the kept ground-truth rows of every
+ * frame; per row gt_ids int32 (0 .. n_ids - 1, unique within a frame), partner_id int32 (the partner's tracker id as the
+ * files name it, -1) and level int32.  Cell (g, f) is (0, 0, 0) when g has no row in frame f, (96, 96, 96) when its row
+ * has level <= alpha_index, else render.PALETTE[partner_id % 64], bytes 0 and 2 swapped for bgr.  One workgroup per
+ * frame; integers only; every byte of the image is written.  Returns 2 when a side of the image exceeds 65535 pixels.
+ * n_ids * n_frames == 0 launches nothing. */
+int clipops_timeline_u8(const int32_t *gt_off, const int32_t *gt_ids, const int32_t *partner_id, const int32_t *level,
+                        int n_ids, int n_frames, int alpha_index, int cell_w, int cell_h, int bgr, uint8_t *image,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

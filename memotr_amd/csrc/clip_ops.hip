@@ -18,7 +18,8 @@
 //   clip_attention.h   multi-head self-attention over the decoder queries, forward and backward
 //   clip_linear.h      the query-sized linears on fp32 MFMA, direct and LDS-staged
 //   clip_tracks.h      result rows, track bank, bank result rows, draw table; the kept-track and the counters rule;
-//                      CLEAR's match events and the error table
+//                      CLEAR's match events and the error table; HOTA's match events, Identity's pairs, the
+//                      per-identity association sums and the identity timeline
 //   clip_fill_gaps.h   gap filling and short-track removal on a result table
 #include <hip/hip_runtime.h>
 #include <stdint.h>

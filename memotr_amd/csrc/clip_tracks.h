@@ -633,6 +633,270 @@ __global__ __launch_bounds__(256) void error_table_kernel(const double *__restri
     for (long p = base + threadIdx.x; p < max_rows; p += 256) draw_table_padding(rows + p * DRAW_ROW_WORDS);
 }
 
+// ---- association analysis (include/clip_ops_hip.h: clipops_hota_events_f64, clipops_identity_pairs_i32,
+//      clipops_assoc_reduce_f64, clipops_timeline_u8) ----
+// HOTA's and Identity's assignments a second time.  trackeval_hota_match and trackeval_identity (track_eval.hip) solve the
+// same problems and keep sums; that library's entry points are fixed, so the two cost views it keeps private are stated
+// here again, on the same assign_core.h, and the pairs are kept.
+constexpr int ASSOC_ALPHAS = CLIPOPS_ASSOC_ALPHAS;
+
+struct AssocAlphas {
+    double v[ASSOC_ALPHAS];
+};
+
+struct HotaEventsView {
+    const double *s, *align;        // the frame's similarity; the sequence's alignment table [G, K]
+    const int32_t *gid, *tid;       // the frame's ids
+    int k, K;
+    __device__ __forceinline__ double at(int i, int j) const {      // (ids are relabelled 0 .. n - 1, as for HotaView)
+#pragma clang fp contract(off)
+        return -(align[(long)gid[i] * K + tid[j]] * s[(size_t)i * k + j]);
+    }
+};
+
+__host__ inline size_t assoc_solve_lds_bytes(int n_rows, int n_cols) {
+    const int mn = n_rows < n_cols ? n_rows : n_cols, mx = n_rows < n_cols ? n_cols : n_rows;
+    return events_align16((size_t)2 * mn * 4) + events_align16(assign::work_bytes(mn, mx));
+}
+
+// One wavefront per frame.  All lanes first write the frame's rows as unmatched; behind the barriers of the solver, lane p
+// of the pair pass overwrites the two rows of pair p and counts the pair into matches[a] for every threshold a < level.
+__global__ __launch_bounds__(64) void hota_events_kernel(const double *__restrict__ sim,
+                                                          const int64_t *__restrict__ sim_off,
+                                                          const int32_t *__restrict__ gt_off,
+                                                          const int32_t *__restrict__ tr_off,
+                                                          const int32_t *__restrict__ gt_ids,
+                                                          const int32_t *__restrict__ tr_ids,
+                                                          const int32_t *__restrict__ frame_seq,
+                                                          const int32_t *__restrict__ n_tr_ids,
+                                                          const int64_t *__restrict__ cell_off,
+                                                          const double *__restrict__ alignment, const AssocAlphas alphas,
+                                                          int max_gt, int max_tr, int mn, int32_t *__restrict__ gt_partner,
+                                                          int32_t *__restrict__ gt_level, int32_t *__restrict__ tr_partner,
+                                                          int32_t *__restrict__ tr_level, int32_t *__restrict__ matches,
+                                                          int32_t *__restrict__ status) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_assoc[];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int g0 = gt_off[f], g = gt_off[f + 1] - g0, k0 = tr_off[f], k = tr_off[f + 1] - k0;
+    int32_t *rows = reinterpret_cast<int32_t *>(s_assoc), *cols = rows + mn;
+    const WaveLanes lanes{lane};
+    lanes.each(g, [&](int i) { gt_partner[g0 + i] = -1; gt_level[g0 + i] = 0; });
+    lanes.each(k, [&](int j) { tr_partner[k0 + j] = -1; tr_level[k0 + j] = 0; });
+    int rc = 0, n = 0;
+    const int s = frame_seq[f];
+    const int K = n_tr_ids[s];
+    const long c0 = cell_off[s], cells = cell_off[s + 1] - c0;
+    const double *sm = sim + sim_off[f];
+    const int32_t *gid = gt_ids + g0, *tid = tr_ids + k0;
+    if (g < 0 || k < 0 || g > max_gt || k > max_tr) {
+        rc = -2;
+    } else if (g > 0 && k > 0) {
+        const HotaEventsView view{sm, alignment + c0, gid, tid, k, K};
+        n = assign::solve_view(lanes, view, g, k, s_assoc + events_align16((size_t)2 * mn * 4), rows, cols);
+        if (n < 0) {
+            rc = -1;
+            n = 0;
+        }
+    }
+    lanes.sync();                                   // the frame's unmatched rows are written; the pairs are visible
+    lanes.each(n, [&](int p) {
+        const int i = rows[p], j = cols[p];
+        const double v = sm[(size_t)i * k + j];
+        int level = 0;
+#pragma unroll
+        for (int a = 0; a < ASSOC_ALPHAS; ++a) level += v >= alphas.v[a] - EVENTS_EPS;
+        if (level == 0) return;
+        gt_partner[g0 + i] = j, gt_level[g0 + i] = level;
+        tr_partner[k0 + j] = i, tr_level[k0 + j] = level;
+        if (!matches) return;
+        const int gi = gid[i], tj = tid[j];
+        const long c = (long)gi * K + tj;
+        if (gi < 0 || (unsigned)tj >= (unsigned)K || c >= cells) return;
+        int32_t *mc = matches + ASSOC_ALPHAS * c0 + c;
+        for (int a = 0; a < level; ++a) atomicAdd(mc + (long)a * cells, 1);
+    });
+    if (lane == 0) status[f] = rc;
+}
+
+// Identity's cost, a function of the counts (evaluation._identity_host's fn + fp): never a matrix in memory
+struct IdentityPairsView {
+    const int32_t *gc, *tc, *idm;   // detections per gt id, per tracker id; frames with sim >= 0.5 per (gt id, tracker id)
+    int G, K;
+    __device__ __forceinline__ double fn(int i, int j) const {
+        if (i >= G) return 0.0;
+        if (j < K) return (double)gc[i] - (double)idm[(long)i * K + j];
+        return j - K == i ? (double)gc[i] : 1e10;
+    }
+    __device__ __forceinline__ double fp(int i, int j) const {
+        if (j >= K) return 0.0;
+        if (i < G) return (double)tc[j] - (double)idm[(long)i * K + j];
+        return i - G == j ? (double)tc[j] : 1e10;
+    }
+    __device__ __forceinline__ double at(int i, int j) const { return fn(i, j) + fp(i, j); }
+};
+
+// One wavefront per sequence: the (G + K) x (G + K) problem; row r < G paired with column c < K is the map g -> k, any
+// other pair leaves its id unmatched.  The problem is square, so every id of either side is in exactly one pair.
+__global__ __launch_bounds__(64) void identity_pairs_kernel(const int32_t *__restrict__ n_gt_ids,
+                                                             const int32_t *__restrict__ n_tr_ids,
+                                                             const int64_t *__restrict__ cell_off,
+                                                             const int32_t *__restrict__ gid_off,
+                                                             const int32_t *__restrict__ tid_off,
+                                                             const int32_t *__restrict__ gt_count,
+                                                             const int32_t *__restrict__ tr_count,
+                                                             const int32_t *__restrict__ id_matches, int max_ids,
+                                                             int32_t *__restrict__ gt_id_partner,
+                                                             int32_t *__restrict__ gt_idtp,
+                                                             int32_t *__restrict__ tr_id_partner,
+                                                             int32_t *__restrict__ tr_idtp, int32_t *__restrict__ status) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_assoc[];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int G = n_gt_ids[s], K = n_tr_ids[s], N = G + K;
+    int32_t *rows = reinterpret_cast<int32_t *>(s_assoc), *cols = rows + max_ids;
+    int32_t *gp = gt_id_partner + gid_off[s], *gtp = gt_idtp + gid_off[s];
+    int32_t *tp = tr_id_partner + tid_off[s], *ttp = tr_idtp + tid_off[s];
+    const int32_t *idm = id_matches + cell_off[s];
+    const WaveLanes lanes{lane};
+    int rc = 0, n = 0;
+    if (G < 0 || K < 0) {                           // (no table of such a sequence has an entry)
+        if (lane == 0) status[s] = -2;
+        return;
+    }
+    lanes.each(G, [&](int i) { gp[i] = -1; gtp[i] = 0; });
+    lanes.each(K, [&](int j) { tp[j] = -1; ttp[j] = 0; });
+    if (N > max_ids) {
+        rc = -2;
+    } else if (G > 0 && K > 0) {                    // (with an empty side every id keeps its own slot)
+        const IdentityPairsView view{gt_count + gid_off[s], tr_count + tid_off[s], idm, G, K};
+        n = assign::solve_view(lanes, view, N, N, s_assoc + events_align16((size_t)2 * max_ids * 4), rows, cols);
+        if (n < 0) {
+            rc = -1;
+            n = 0;
+        }
+    }
+    lanes.sync();
+    lanes.each(n, [&](int p) {
+        const int r = rows[p], c = cols[p];
+        if (r < G && c < K) {
+            const int both = idm[(long)r * K + c];
+            gp[r] = c, gtp[r] = both;
+            tp[c] = r, ttp[c] = both;
+        }
+    });
+    if (lane == 0) status[s] = rc;
+}
+
+__device__ __forceinline__ double assoc_wave_sum_f64(double v) {     // a fixed xor tree: the same bits on every lane
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// One wavefront per (id, sequence, side).  Lane l walks the other side's ids l, l + 64, ... in ascending order; integer
+// sums meet in shuffles, double sums are the lanes' partials through the fixed tree above.
+__global__ __launch_bounds__(64) void assoc_reduce_kernel(const int32_t *__restrict__ n_gt_ids,
+                                                           const int32_t *__restrict__ n_tr_ids,
+                                                           const int64_t *__restrict__ cell_off,
+                                                           const int32_t *__restrict__ gid_off,
+                                                           const int32_t *__restrict__ tid_off,
+                                                           const int32_t *__restrict__ gt_count,
+                                                           const int32_t *__restrict__ tr_count,
+                                                           const int32_t *__restrict__ matches, int a0,
+                                                           int32_t *__restrict__ gt_tp, double *__restrict__ gt_num,
+                                                           int32_t *__restrict__ gt_top, int32_t *__restrict__ tr_tp,
+                                                           double *__restrict__ tr_num, int32_t *__restrict__ tr_top) {
+#pragma clang fp contract(off)
+    const int id = blockIdx.x, s = blockIdx.y, side = blockIdx.z, lane = threadIdx.x;
+    const int G = n_gt_ids[s], K = n_tr_ids[s];
+    const int n_mine = side ? K : G, n_other = side ? G : K;
+    if (id >= n_mine) return;
+    const long c0 = cell_off[s], cells = (long)G * K;
+    const int32_t *gc = gt_count + gid_off[s], *tc = tr_count + tid_off[s];
+    const long row = (long)(side ? tid_off[s] : gid_off[s]) + id;
+    int32_t *o_tp = (side ? tr_tp : gt_tp) + row * ASSOC_ALPHAS;
+    double *o_num = (side ? tr_num : gt_num) + row * 2 * ASSOC_ALPHAS;
+    int32_t *o_top = (side ? tr_top : gt_top) + row * 3;
+    const double mine = (double)(side ? tc[id] : gc[id]);
+    const long stride = side ? K : 1, first = side ? id : (long)id * K;     // the cell of (id, other) in [G, K]
+    for (int a = 0; a < ASSOC_ALPHAS; ++a) {
+        const int32_t *mc = matches + ASSOC_ALPHAS * c0 + (long)a * cells + first;
+        int tp = 0, partners = 0, top = -1, top_count = 0;
+        double ass = 0.0, part = 0.0;
+        for (int o = lane; o < n_other; o += 64) {
+            const int mi = mc[(long)o * stride];
+            const double m = (double)mi, theirs = (double)(side ? gc[o] : tc[o]);
+            const double d = mine + theirs - m;
+            ass += m * (m / (d > 1.0 ? d : 1.0));
+            part += m * (m / (mine > 1.0 ? mine : 1.0));
+            tp += mi;
+            partners += mi > 0;
+            if (mi > top_count) top = o, top_count = mi;            // (ascending ids: a tie keeps the lower one)
+        }
+        tp = wave_sum_i32(tp);
+        ass = assoc_wave_sum_f64(ass);
+        part = assoc_wave_sum_f64(part);
+        if (a == a0) {
+            partners = wave_sum_i32(partners);
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const int oc = __shfl_xor(top_count, off, 64), ot = __shfl_xor(top, off, 64);
+                if (oc > top_count || (oc == top_count && oc > 0 && ot < top)) top = ot, top_count = oc;
+            }
+            if (lane == 0) o_top[0] = partners, o_top[1] = top, o_top[2] = top_count;
+        }
+        if (lane == 0) {
+            o_tp[a] = tp;
+            o_num[a] = ass;
+            o_num[ASSOC_ALPHAS + a] = part;
+        }
+    }
+}
+
+// One workgroup per frame: the colour of every identity in this frame's column is built in LDS (black, grey for a row
+// that is no true positive at alpha_index, else the partner's palette colour), TIMELINE_IDS identities a pass; then the
+// cell_w-wide strip of those identities is stored.  Ids are unique within a frame, so no two rows write one entry.
+constexpr int TIMELINE_IDS = 8192;
+
+__global__ __launch_bounds__(256) void timeline_kernel(const int32_t *__restrict__ gt_off,
+                                                       const int32_t *__restrict__ gt_ids,
+                                                       const int32_t *__restrict__ partner_id,
+                                                       const int32_t *__restrict__ level, int G, int n_frames,
+                                                       int alpha_index, int cell_w, int cell_h, int bgr,
+                                                       uint8_t *__restrict__ image) {
+    __shared__ int colour[TIMELINE_IDS];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int r0 = gt_off[f], n = gt_off[f + 1] - r0;
+    const size_t pitch = (size_t)n_frames * cell_w * 3;
+    for (int base = 0; base < G; base += TIMELINE_IDS) {             // (G is uniform: every thread makes every trip)
+        const int ids = min(TIMELINE_IDS, G - base);
+        for (int i = tid; i < ids; i += 256) colour[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            const int g = gt_ids[r0 + i] - base;
+            if (g < 0 || g >= ids) continue;
+            const int p = partner_id[r0 + i];
+            int c = 96 | 96 << 8 | 96 << 16;
+            if (level[r0 + i] > alpha_index && p >= 0) {
+                c = draw_table_palette(p & 63);
+                if (bgr) c = (c & 0xFF00) | (c & 0xFF) << 16 | (c >> 16 & 0xFF);
+            }
+            colour[g] = c;
+        }
+        __syncthreads();
+        const int per_id = cell_h * cell_w;
+        for (long e = tid; e < (long)ids * per_id; e += 256) {
+            const int g = (int)(e / per_id), q = (int)(e - (long)g * per_id), y = q / cell_w, x = q - y * cell_w;
+            const int c = colour[g];
+            uint8_t *px = image + ((size_t)(base + g) * cell_h + y) * pitch + ((size_t)f * cell_w + x) * 3;
+            px[0] = (uint8_t)(c & 0xFF), px[1] = (uint8_t)(c >> 8 & 0xFF), px[2] = (uint8_t)(c >> 16 & 0xFF);
+        }
+        __syncthreads();                            // colour is written again by the next pass
+    }
+}
+
 // The argument checks the scalar and the per-stream entry points of the bank share, reported under the caller's name:
 // 1 = launch, 0 = nothing to do (ok() is set), -code = fail()'s code.
 int bank_update_args(const char *who, const clipops_bank_model *model, const clipops_bank *bank, int B, int n_det, int cap,
@@ -781,5 +1045,84 @@ int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, cons
         return fail(1, who, "null pointer");
     return launch("error_table_kernel", error_table_kernel, dim3(n_frames), dim3(256), 0, stream, gt_boxes, tr_boxes,
                   gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind, max_rows, width, bgr ? 1 : 0, font_scale, table) ? 3 : 0;
+}
+
+int clipops_hota_events_f64(const double *sim, const int64_t *sim_off, const int32_t *gt_off, const int32_t *tr_off,
+                            const int32_t *gt_ids, const int32_t *tr_ids, const int32_t *frame_seq, int n_frames,
+                            const int32_t *n_tr_ids, const int64_t *cell_off, const double *alignment,
+                            const double *alphas, int max_gt, int max_tr, int32_t *gt_partner, int32_t *gt_level,
+                            int32_t *tr_partner, int32_t *tr_level, int32_t *matches, int32_t *status, void *stream) {
+    const char *who = "clipops_hota_events_f64";
+    if (n_frames < 0 || max_gt < 0 || max_tr < 0) return fail(1, who, "negative size");
+    if (max_gt > CLIPOPS_EVENTS_MAX_DIM || max_tr > CLIPOPS_EVENTS_MAX_DIM)
+        return fail(2, who, "a frame exceeds CLIPOPS_EVENTS_MAX_DIM = 2048");
+    if (n_frames == 0) return ok();
+    if (!sim || !sim_off || !gt_off || !tr_off || !gt_ids || !tr_ids || !frame_seq || !n_tr_ids || !cell_off ||
+        !alignment || !alphas || !gt_partner || !gt_level || !tr_partner || !tr_level || !status)
+        return fail(1, who, "null pointer");
+    AssocAlphas a;
+    for (int i = 0; i < ASSOC_ALPHAS; ++i) a.v[i] = alphas[i];
+    static std::atomic<unsigned long long> allowed{0};
+    const size_t lds = assoc_solve_lds_bytes(max_gt, max_tr);           // (at most 100 KiB at the largest sizes)
+    if (allow_lds(reinterpret_cast<const void *>(hota_events_kernel), lds, allowed)) return 3;
+    return launch("hota_events_kernel", hota_events_kernel, dim3(n_frames), dim3(64), lds, stream, sim, sim_off, gt_off,
+                  tr_off, gt_ids, tr_ids, frame_seq, n_tr_ids, cell_off, alignment, a, max_gt, max_tr,
+                  max_gt < max_tr ? max_gt : max_tr, gt_partner, gt_level, tr_partner, tr_level, matches, status) ? 3 : 0;
+}
+
+int clipops_identity_pairs_i32(int n_seqs, const int32_t *n_gt_ids, const int32_t *n_tr_ids, const int64_t *cell_off,
+                               const int32_t *gid_off, const int32_t *tid_off, const int32_t *gt_count,
+                               const int32_t *tr_count, const int32_t *id_matches, int max_ids, int32_t *gt_id_partner,
+                               int32_t *gt_idtp, int32_t *tr_id_partner, int32_t *tr_idtp, int32_t *status,
+                               void *stream) {
+    const char *who = "clipops_identity_pairs_i32";
+    if (n_seqs < 0 || max_ids < 0) return fail(1, who, "negative size");
+    if (max_ids > CLIPOPS_EVENTS_MAX_DIM)
+        return fail(2, who, "ground-truth plus tracker ids of a sequence exceed CLIPOPS_EVENTS_MAX_DIM = 2048");
+    if (n_seqs == 0) return ok();
+    if (!n_gt_ids || !n_tr_ids || !cell_off || !gid_off || !tid_off || !gt_count || !tr_count || !id_matches ||
+        !gt_id_partner || !gt_idtp || !tr_id_partner || !tr_idtp || !status)
+        return fail(1, who, "null pointer");
+    static std::atomic<unsigned long long> allowed{0};
+    const size_t lds = assoc_solve_lds_bytes(max_ids, max_ids);
+    if (allow_lds(reinterpret_cast<const void *>(identity_pairs_kernel), lds, allowed)) return 3;
+    return launch("identity_pairs_kernel", identity_pairs_kernel, dim3(n_seqs), dim3(64), lds, stream, n_gt_ids, n_tr_ids,
+                  cell_off, gid_off, tid_off, gt_count, tr_count, id_matches, max_ids, gt_id_partner, gt_idtp,
+                  tr_id_partner, tr_idtp, status) ? 3 : 0;
+}
+
+int clipops_assoc_reduce_f64(int n_seqs, const int32_t *n_gt_ids, const int32_t *n_tr_ids, const int64_t *cell_off,
+                             const int32_t *gid_off, const int32_t *tid_off, const int32_t *gt_count,
+                             const int32_t *tr_count, const int32_t *matches, int max_side_ids, int alpha_index,
+                             int32_t *gt_tp, double *gt_num, int32_t *gt_top, int32_t *tr_tp, double *tr_num,
+                             int32_t *tr_top, void *stream) {
+    const char *who = "clipops_assoc_reduce_f64";
+    if (n_seqs < 0 || max_side_ids < 0) return fail(1, who, "negative size");
+    if (alpha_index < 0 || alpha_index >= CLIPOPS_ASSOC_ALPHAS) return fail(1, who, "alpha_index outside 0 .. 18");
+    if (n_seqs > 65535) return fail(2, who, "more than 65535 sequences in one call");
+    if (max_side_ids > CLIPOPS_EVENTS_MAX_DIM)
+        return fail(2, who, "the ids of a sequence exceed CLIPOPS_EVENTS_MAX_DIM = 2048");
+    if (n_seqs == 0 || max_side_ids == 0) return ok();
+    if (!n_gt_ids || !n_tr_ids || !cell_off || !gid_off || !tid_off || !gt_count || !tr_count || !matches || !gt_tp ||
+        !gt_num || !gt_top || !tr_tp || !tr_num || !tr_top)
+        return fail(1, who, "null pointer");
+    return launch("assoc_reduce_kernel", assoc_reduce_kernel, dim3(max_side_ids, n_seqs, 2), dim3(64), 0, stream,
+                  n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, matches, alpha_index, gt_tp, gt_num,
+                  gt_top, tr_tp, tr_num, tr_top) ? 3 : 0;
+}
+
+int clipops_timeline_u8(const int32_t *gt_off, const int32_t *gt_ids, const int32_t *partner_id, const int32_t *level,
+                        int n_ids, int n_frames, int alpha_index, int cell_w, int cell_h, int bgr, uint8_t *image,
+                        void *stream) {
+    const char *who = "clipops_timeline_u8";
+    if (n_ids < 0 || n_frames < 0) return fail(1, who, "negative size");
+    if (cell_w < 1 || cell_h < 1) return fail(1, who, "cell_w or cell_h below 1");
+    if (alpha_index < 0 || alpha_index >= CLIPOPS_ASSOC_ALPHAS) return fail(1, who, "alpha_index outside 0 .. 18");
+    if ((long)n_ids * cell_h > 65535 || (long)n_frames * cell_w > 65535)
+        return fail(2, who, "the image exceeds 65535 pixels on a side");
+    if (n_ids == 0 || n_frames == 0) return ok();
+    if (!gt_off || !gt_ids || !partner_id || !level || !image) return fail(1, who, "null pointer");
+    return launch("timeline_kernel", timeline_kernel, dim3(n_frames), dim3(256), 0, stream, gt_off, gt_ids, partner_id,
+                  level, n_ids, n_frames, alpha_index, cell_w, cell_h, bgr ? 1 : 0, image) ? 3 : 0;
 }
 }  // extern "C"

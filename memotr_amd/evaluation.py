@@ -647,6 +647,13 @@ class TrackingEvaluator:
         from .diagnose import clear_events
         return clear_events(pack_sequences(self.sequences()), self.benchmark, device=self.device)
 
+    def association(self, alpha_index: int = 9) -> Dict[str, object]:
+        """``{name: association.SequenceAssociation}`` of what was collected: HOTA's matches per row, the per-identity
+        association scores and the Identity metric's map."""
+        from .association import association
+        return association(pack_sequences(self.sequences()), self.benchmark, device=self.device,
+                           alpha_index=alpha_index)
+
 
 # ------------------------------------------------------------------------------------------------------ text files
 def read_mot_txt(path: str) -> np.ndarray:
