@@ -537,6 +537,31 @@ int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, cons
                             int n_frames, int max_rows, int width, int height, int bgr, int font_scale, int32_t *table,
                             void *stream);
 
+/* ---- BDD100K error analysis: the cross-class pairs of a frame ----
+ * (Added without a new CLIPOPS_ABI_VERSION, like the error-analysis entries: no entry point changed.)
+ * BDD100K scores every class on its own, so a car labelled truck is a MISS of `car` and an FP of `truck`.
+ * clipops_bdd_cross_class_f64 finds such boxes (memotr_amd/diagnose_bdd100k.py: _cross_host).  It reads the rows as
+ * evaluation_bdd100k.PackedBDD gives them, frame-major: gt_boxes / tr_boxes float64 (n, 4) x0, y0, x1, y1; gt_classes /
+ * tr_classes int32 TrackEval's class ids (include/track_eval_bdd_hip.h); gt_off / tr_off int32 [F + 1]; gt_kind / tr_kind
+ * int32 the CLIPOPS_KIND_* of every row.
+ *   frame     the candidates are the ground-truth rows of kind MISS and the tracker rows of kind FP whose class is one of
+ *             the 8 evaluated, each side in input order.  score(i, j) is 0 for two rows of one class, else their IoU
+ *             (bddeval_similarity's operation order: the same bits) with values < 0.5 - eps set to 0.  The pairs are
+ *             scipy.optimize.linear_sum_assignment(-score)'s (assign_core.h); a pair counts when its score is > eps.
+ *   output    per row of either side: partner int32 the paired row's index within its frame, -1; class int32 the paired
+ *             row's class index 0 .. 7, -1; iou float64 the pair's IoU, 0.  status int32 [F]: 0, -1 no feasible
+ *             assignment, -2 more candidates on a side than max_gt / max_tr (the frame's rows are then all -1 / -1 / 0).
+ *             Every entry of the seven arrays is written.
+ * One wavefront per frame; candidates and solver state in LDS (dynamic, above 64 KiB by opt-in).  max_gt / max_tr at most
+ * CLIPOPS_EVENTS_MAX_DIM.  n_frames == 0 launches nothing.  Arguments are checked on the host without touching a device:
+ * returns 1 for a negative size or a null pointer with n_frames > 0, 2 for a size above CLIPOPS_EVENTS_MAX_DIM, 3 when the
+ * launch failed. */
+int clipops_bdd_cross_class_f64(const double *gt_boxes, const double *tr_boxes, const int32_t *gt_classes,
+                                const int32_t *tr_classes, const int32_t *gt_off, const int32_t *tr_off,
+                                const int32_t *gt_kind, const int32_t *tr_kind, int n_frames, int max_gt, int max_tr,
+                                int32_t *gt_partner, int32_t *gt_class, double *gt_iou, int32_t *tr_partner,
+                                int32_t *tr_class, double *tr_iou, int32_t *status, void *stream);
+
 /* ---- association analysis: HOTA's and Identity's matches kept, reduced per identity, drawn as a timeline ----
  * (Added without a new CLIPOPS_ABI_VERSION, like the error-analysis entries: no entry point changed.)
  * The four entries work on the preprocessed, compacted arrays and the per-sequence tables of include/track_eval_hip.h

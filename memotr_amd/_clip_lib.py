@@ -71,6 +71,7 @@ SYMBOLS = {
                                                                  c_void_p], c_int),
     "clipops_clear_events_f64": ([c_void_p] * 7 + [c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 6, c_int),
     "clipops_error_table_f64": ([c_void_p] * 8 + [c_int] * 6 + [c_void_p, c_void_p], c_int),
+    "clipops_bdd_cross_class_f64": ([c_void_p] * 8 + [c_int] * 3 + [c_void_p] * 8, c_int),
     "clipops_hota_events_f64": ([c_void_p] * 7 + [c_int] + [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 7, c_int),
     "clipops_identity_pairs_i32": ([c_int] + [c_void_p] * 8 + [c_int] + [c_void_p] * 6, c_int),
     "clipops_assoc_reduce_f64": ([c_int] + [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 7, c_int),

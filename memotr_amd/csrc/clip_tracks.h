@@ -1,6 +1,6 @@
 // clip_tracks.h -- the device side of the online tracker and of the submit path: result rows, the track bank, the
 // bank's result rows, the overlay's draw table, and the error analysis (CLEAR's match events, the draw table coloured
-// by event).  One statement of the kept-track rule and of the counters' capacity rule serves the first four (and
+// by event; the cross-class pairs of BDD100K).  One statement of the kept-track rule and of the counters' capacity rule serves the first four (and
 // clip_fill_gaps.h, included after this header); one statement of a draw-table row serves both tables.
 // Included by clip_ops.hip after clip_common.h.
 #pragma once
@@ -633,6 +633,129 @@ __global__ __launch_bounds__(256) void error_table_kernel(const double *__restri
     for (long p = base + threadIdx.x; p < max_rows; p += 256) draw_table_padding(rows + p * DRAW_ROW_WORDS);
 }
 
+// ---- BDD100K error analysis (include/clip_ops_hip.h: clipops_bdd_cross_class_f64) ----
+// What the per-class walks cannot see: a box that is a MISS in one class and a false positive in another.  One wavefront
+// per input frame pairs the frame's MISS rows with its FP rows of a DIFFERENT class, maximising the summed IoU.
+// TrackEval's class id -> class index in its order of evaluation, -1: not evaluated (as track_eval_bdd.hip)
+__device__ __forceinline__ int bdd_class_index(int id) {
+    switch (id) {
+        case 1: return 0;       // pedestrian
+        case 2: return 1;       // rider
+        case 4: return 2;       // car
+        case 5: return 3;       // bus
+        case 6: return 4;       // truck
+        case 7: return 5;       // train
+        case 10: return 6;      // motorcycle
+        case 11: return 7;      // bicycle
+        default: return -1;
+    }
+}
+
+// the candidates of a frame, compacted into LDS in order of appearance: row within the frame, class index
+struct CrossSide {
+    const double *boxes;        // the frame's first box
+    const int32_t *row, *cls;   // [n] LDS
+};
+
+// IoU of corner boxes in the operation order of track_eval_bdd.hip's similarity_kernel (the same bits), thresholded by
+// the project's rule; 0 for two rows of one class
+struct CrossView {
+    CrossSide g, t;
+    __device__ __forceinline__ double score(int i, int j) const {
+#pragma clang fp contract(off)                      // (the areas' products must not fuse into the union's sum)
+        if (g.cls[i] == t.cls[j]) return 0.0;
+        const double *a = g.boxes + (size_t)g.row[i] * 4, *b = t.boxes + (size_t)t.row[j] * 4;
+        const double ax0 = a[0], ay0 = a[1], ax1 = a[2], ay1 = a[3];
+        const double bx0 = b[0], by0 = b[1], bx1 = b[2], by1 = b[3];
+        const double w = (ax1 < bx1 ? ax1 : bx1) - (ax0 > bx0 ? ax0 : bx0);
+        const double h = (ay1 < by1 ? ay1 : by1) - (ay0 > by0 ? ay0 : by0);
+        double inter = (w > 0.0 ? w : 0.0) * (h > 0.0 ? h : 0.0);
+        const double area1 = (ax1 - ax0) * (ay1 - ay0), area2 = (bx1 - bx0) * (by1 - by0);
+        double uni = area1 + area2 - inter;
+        if (area1 <= EVENTS_EPS || area2 <= EVENTS_EPS || uni <= EVENTS_EPS) inter = 0.0;
+        if (uni <= EVENTS_EPS) uni = 1.0;
+        const double v = inter / uni;
+        return v < EVENTS_THRESHOLD - EVENTS_EPS ? 0.0 : v;
+    }
+    __device__ __forceinline__ double at(int i, int j) const { return -score(i, j); }
+};
+
+// LDS of one frame: the pair lists (2 * mn int32), row and class of the candidates of both sides, the solver's scratch
+__host__ inline size_t cross_lds_bytes(int max_gt, int max_tr) {
+    const int mn = max_gt < max_tr ? max_gt : max_tr, mx = max_gt < max_tr ? max_tr : max_gt;
+    return events_align16((size_t)2 * mn * 4) + events_align16((size_t)2 * (max_gt + max_tr) * 4) +
+           events_align16(assign::work_bytes(mn, mx));
+}
+
+// Rows of `kinds[0 .. n)` equal to `want` whose class is evaluated, 64 per ballot, into row / cls while they fit `cap`;
+// returns their number (wave-uniform).  Every row's three outputs get the values of "no partner" on the way.
+__device__ __forceinline__ int cross_compact(const int32_t *__restrict__ kinds, const int32_t *__restrict__ classes, int n,
+                                             int want, int cap, int lane, int32_t *row, int32_t *cls,
+                                             int32_t *__restrict__ partner, int32_t *__restrict__ partner_class,
+                                             double *__restrict__ iou) {
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int total = 0;
+    for (int base = 0; base < n; base += 64) {              // (wave-uniform trip count: every lane votes)
+        const int i = base + lane;
+        int ci = -1;
+        if (i < n) {
+            partner[i] = -1, partner_class[i] = -1, iou[i] = 0.0;
+            if (kinds[i] == want) ci = bdd_class_index(classes[i]);
+        }
+        const unsigned long long votes = __ballot(ci >= 0);
+        const int at = total + __popcll(votes & below);
+        if (ci >= 0 && at < cap) row[at] = i, cls[at] = ci;
+        total += __popcll(votes);
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(64) void bdd_cross_class_kernel(const double *__restrict__ gt_boxes,
+                                                              const double *__restrict__ tr_boxes,
+                                                              const int32_t *__restrict__ gt_classes,
+                                                              const int32_t *__restrict__ tr_classes,
+                                                              const int32_t *__restrict__ gt_off,
+                                                              const int32_t *__restrict__ tr_off,
+                                                              const int32_t *__restrict__ gt_kind,
+                                                              const int32_t *__restrict__ tr_kind, int max_gt, int max_tr,
+                                                              int mn, int32_t *__restrict__ gt_partner,
+                                                              int32_t *__restrict__ gt_class, double *__restrict__ gt_iou,
+                                                              int32_t *__restrict__ tr_partner,
+                                                              int32_t *__restrict__ tr_class, double *__restrict__ tr_iou,
+                                                              int32_t *__restrict__ status) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_cross[];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int g0 = gt_off[f], g = gt_off[f + 1] - g0, k0 = tr_off[f], k = tr_off[f + 1] - k0;
+    int32_t *rows = reinterpret_cast<int32_t *>(s_cross), *cols = rows + mn;
+    int32_t *g_row = reinterpret_cast<int32_t *>(s_cross + events_align16((size_t)2 * mn * 4));
+    int32_t *g_cls = g_row + max_gt, *t_row = g_cls + max_gt, *t_cls = t_row + max_tr;
+    unsigned char *work = s_cross + events_align16((size_t)2 * mn * 4) + events_align16((size_t)2 * (max_gt + max_tr) * 4);
+    const WaveLanes lanes{lane};
+    const int ng = cross_compact(gt_kind + g0, gt_classes + g0, g, CLIPOPS_KIND_MISS, max_gt, lane, g_row, g_cls,
+                                 gt_partner + g0, gt_class + g0, gt_iou + g0);
+    const int nt = cross_compact(tr_kind + k0, tr_classes + k0, k, CLIPOPS_KIND_FP, max_tr, lane, t_row, t_cls,
+                                 tr_partner + k0, tr_class + k0, tr_iou + k0);
+    lanes.sync();                                   // the candidates and the rows' "no partner" are written
+    int rc = 0;
+    if (ng > max_gt || nt > max_tr) {
+        rc = -2;
+    } else if (ng > 0 && nt > 0) {
+        const CrossView view{{gt_boxes + (size_t)g0 * 4, g_row, g_cls}, {tr_boxes + (size_t)k0 * 4, t_row, t_cls}};
+        const int n = assign::solve_view(lanes, view, ng, nt, work, rows, cols);
+        if (n < 0) rc = -1;
+        lanes.each(n, [&](int p) {                  // (n < 0: no trip)
+            const int i = rows[p], j = cols[p];
+            const double v = view.score(i, j);
+            if (!(v > EVENTS_EPS)) return;
+            const int gi = g0 + g_row[i], tj = k0 + t_row[j];
+            gt_partner[gi] = t_row[j], gt_class[gi] = t_cls[j], gt_iou[gi] = v;
+            tr_partner[tj] = g_row[i], tr_class[tj] = g_cls[i], tr_iou[tj] = v;
+        });
+    }
+    if (lane == 0) status[f] = rc;
+}
+
 // ---- association analysis (include/clip_ops_hip.h: clipops_hota_events_f64, clipops_identity_pairs_i32,
 //      clipops_assoc_reduce_f64, clipops_timeline_u8) ----
 // HOTA's and Identity's assignments a second time.  trackeval_hota_match and trackeval_identity (track_eval.hip) solve the
@@ -1045,6 +1168,28 @@ int clipops_error_table_f64(const double *gt_boxes, const double *tr_boxes, cons
         return fail(1, who, "null pointer");
     return launch("error_table_kernel", error_table_kernel, dim3(n_frames), dim3(256), 0, stream, gt_boxes, tr_boxes,
                   gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind, max_rows, width, bgr ? 1 : 0, font_scale, table) ? 3 : 0;
+}
+
+int clipops_bdd_cross_class_f64(const double *gt_boxes, const double *tr_boxes, const int32_t *gt_classes,
+                                const int32_t *tr_classes, const int32_t *gt_off, const int32_t *tr_off,
+                                const int32_t *gt_kind, const int32_t *tr_kind, int n_frames, int max_gt, int max_tr,
+                                int32_t *gt_partner, int32_t *gt_class, double *gt_iou, int32_t *tr_partner,
+                                int32_t *tr_class, double *tr_iou, int32_t *status, void *stream) {
+    const char *who = "clipops_bdd_cross_class_f64";
+    if (n_frames < 0 || max_gt < 0 || max_tr < 0) return fail(1, who, "negative size");
+    if (max_gt > CLIPOPS_EVENTS_MAX_DIM || max_tr > CLIPOPS_EVENTS_MAX_DIM)
+        return fail(2, who, "a candidate count exceeds CLIPOPS_EVENTS_MAX_DIM = 2048");
+    if (n_frames == 0) return ok();
+    if (!gt_boxes || !tr_boxes || !gt_classes || !tr_classes || !gt_off || !tr_off || !gt_kind || !tr_kind ||
+        !gt_partner || !gt_class || !gt_iou || !tr_partner || !tr_class || !tr_iou || !status)
+        return fail(1, who, "null pointer");
+    static std::atomic<unsigned long long> allowed{0};
+    const size_t lds = cross_lds_bytes(max_gt, max_tr);                 // (at most 132 KiB at the largest sizes)
+    if (allow_lds(reinterpret_cast<const void *>(bdd_cross_class_kernel), lds, allowed)) return 3;
+    return launch("bdd_cross_class_kernel", bdd_cross_class_kernel, dim3(n_frames), dim3(64), lds, stream, gt_boxes,
+                  tr_boxes, gt_classes, tr_classes, gt_off, tr_off, gt_kind, tr_kind, max_gt, max_tr,
+                  max_gt < max_tr ? max_gt : max_tr, gt_partner, gt_class, gt_iou, tr_partner, tr_class, tr_iou,
+                  status) ? 3 : 0;
 }
 
 int clipops_hota_events_f64(const double *sim, const int64_t *sim_off, const int32_t *gt_off, const int32_t *tr_off,

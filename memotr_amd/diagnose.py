@@ -28,7 +28,7 @@ Kinds.  A ground-truth row is IGNORED (removed by the preprocessing: not a pedes
 preprocessing), TP (= MATCH), SWITCH (a TP whose partner is a SWITCH) or FP.
 
 Scope: ``benchmark="MOT17"`` (DanceTrack, SportsMOT, MOT17) and ``"MOT15"`` (no preprocessing), as ``evaluation.py``.
-BDD100K is out of scope: its evaluator (evaluation_bdd100k.py) is a separate library with a fixed interface.
+BDD100K's events are diagnose_bdd100k.py's: eight problems per sequence, ignore regions and class confusions.
 """
 from __future__ import annotations
 
@@ -270,8 +270,8 @@ def _split(p: E.PackedSequences, rows: dict) -> Dict[str, SequenceEvents]:
 def clear_events_host(packed: E.PackedSequences, benchmark: str = "MOT17") -> dict:
     """The events of every input row of ``packed`` (see the module's text), as numpy arrays over all sequences:
     ``gt_kind``, ``gt_frag``, ``gt_partner``, ``gt_iou``, ``tr_kind``, ``tr_partner``, and ``counts`` int32 [S, 5]
-    (CLR_TP, CLR_FN, CLR_FP, IDSW, Frag).  MOT17 rules, or MOT15 without preprocessing; not BDD100K (a separate
-    evaluator, evaluation_bdd100k.py)."""
+    (CLR_TP, CLR_FN, CLR_FP, IDSW, Frag).  MOT17 rules, or MOT15 without preprocessing; not BDD100K
+    (diagnose_bdd100k.py)."""
     import torch
     _check_benchmark(benchmark)
     p = packed.numpy()
@@ -286,7 +286,7 @@ def clear_events_host(packed: E.PackedSequences, benchmark: str = "MOT17") -> di
 def _check_benchmark(benchmark: str) -> None:
     if benchmark not in ("MOT17", "MOT15"):
         raise ValueError(f"benchmark {benchmark!r} is not supported (MOT17 rules, or MOT15 for no preprocessing match; "
-                         "BDD100K's events are out of scope)")
+                         "BDD100K's events are memotr_amd.diagnose_bdd100k's)")
 
 
 # ------------------------------------------------------------------------------------------------ the device path

@@ -565,6 +565,12 @@ class BDD100KEvaluator:
     def evaluate(self) -> Dict[str, dict]:
         return evaluate_packed_bdd(pack_bdd(self.sequences()), device=self.device if self.device else "cpu")
 
+    def events(self) -> Dict[str, object]:
+        """``{name: diagnose_bdd100k.BDDSequenceEvents}`` of what was collected: the decisions behind the per-class
+        CLEAR counts, per row, the tracker boxes dropped inside ignore regions and the class confusions."""
+        from .diagnose_bdd100k import bdd_events
+        return bdd_events(pack_bdd(self.sequences()), device=self.device)
+
 
 def _read_frames(path: str) -> list:
     with open(path) as f:
@@ -573,8 +579,9 @@ def _read_frames(path: str) -> list:
     return sorted(frames, key=lambda fr: fr[key])
 
 
-def evaluate_bdd_files(gt_dir: str, tracker_dir: str, device=None) -> Dict[str, dict]:
-    """Score result files: one ``<seq>.json`` per sequence in ``gt_dir`` and in ``tracker_dir``, each a list of frames
+def load_bdd_files(gt_dir: str, tracker_dir: str, device=None) -> BDD100KEvaluator:
+    """Result files as a filled ``BDD100KEvaluator`` (``evaluate_bdd_files`` scores it, ``diagnose_bdd100k`` asks it for
+    the events): one ``<seq>.json`` per sequence in ``gt_dir`` and in ``tracker_dir``, each a list of frames
     ``{"index" | "frameIndex", "labels": [{"id", "category", "box2d": {"x1", "y1", "x2", "y2"}, "attributes":
     {"Crowd": bool}}]}``.  Frames are sorted by ``index`` where every frame has it, else by ``frameIndex``: TrackEval
     reads the first, the reference's writer (``SequenceTracker.bdd_frame_result``) emits the second, so both are
@@ -600,7 +607,12 @@ def evaluate_bdd_files(gt_dir: str, tracker_dir: str, device=None) -> Dict[str, 
             ev.add_tracker_rows(seq, t, [int(a["id"]) for a in labels], [box(a) for a in labels],
                                 [a["category"] for a in labels])
         ev._gt.setdefault(seq, {})
-    return ev.evaluate()
+    return ev
+
+
+def evaluate_bdd_files(gt_dir: str, tracker_dir: str, device=None) -> Dict[str, dict]:
+    """Score result files in ``load_bdd_files``' layout."""
+    return load_bdd_files(gt_dir, tracker_dir, device).evaluate()
 
 
 # ------------------------------------------------------------------------------------------------- synthetic data
