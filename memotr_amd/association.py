@@ -18,9 +18,9 @@ Frames are numbered from 1 wherever this module names one, as in ``diagnose``.
 
 The definition is stated twice, like the evaluation's.  ``association_host`` repeats ``evaluation._hota_host``'s second
 loop and ``evaluation._identity_host``'s assignment after ``evaluation._preprocess_host`` and keeps the pairs; it is
-numpy and scipy.  With a CUDA ``device`` the similarity, the preprocessing match, the compaction and
-``trackeval_accumulate`` run as ``evaluation.device_tables`` runs them, and four kernels of
-memotr_amd/csrc/clip_tracks.h do the rest: ``clipops_hota_events_f64`` (one wavefront per frame),
+numpy and scipy.  With a CUDA ``device`` the similarity, the preprocessing match and the compaction are
+``evaluation.device_front``'s and ``trackeval_accumulate`` is ``evaluation.device_accumulate``'s, the calls
+``evaluation.device_tables`` stands on, and four kernels of memotr_amd/csrc/clip_tracks.h do the rest: ``clipops_hota_events_f64`` (one wavefront per frame),
 ``clipops_identity_pairs_i32`` (one per sequence), ``clipops_assoc_reduce_f64`` (one per identity) and
 ``clipops_timeline_u8`` (one workgroup per frame).  Integer results and similarities agree exactly, the per-identity
 float sums to float64 summation order.
@@ -395,23 +395,6 @@ def _split(p: E.PackedSequences, t: dict, alpha_index: int) -> Dict[str, Sequenc
 
 
 # ------------------------------------------------------------------------------------------------ the device path
-def _ptr(t, nothing):
-    return t.data_ptr() if t.numel() else nothing.data_ptr()
-
-
-def _launch(name: str, dev, tensors_and_ints, spare=None) -> None:
-    """One entry point of libclip_ops_hip.so on the current stream of ``dev``: tensors become addresses (an empty one the
-    address of ``spare``, a two-word array the caller keeps; allocated here when there is none), ``None`` a null pointer,
-    everything else is passed as it is."""
-    import torch
-    from . import _clip_lib as C
-    with torch.cuda.device(dev):
-        if spare is None:
-            spare = torch.zeros(2, dtype=torch.float64, device=dev)
-        args = [_ptr(a, spare) if hasattr(a, "data_ptr") else a for a in tensors_and_ints]
-        C.check(getattr(C.lib, name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)
-
-
 def launch_hota_events(sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, frame_seq, n_tr_ids, cell_off, alignment,
                        max_gt: int, max_tr: int, gt_partner, gt_level, tr_partner, tr_level, matches, status,
                        spare=None) -> None:
@@ -419,116 +402,50 @@ def launch_hota_events(sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, frame_seq, 
     include/clip_ops_hip.h; the five outputs are written whole, ``matches`` (zeroed by the caller, or None) is
     incremented; nothing waits."""
     alphas = np.ascontiguousarray(E.ALPHAS, np.float64)
-    _launch("clipops_hota_events_f64", sim.device,
-            [sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, frame_seq, int(gt_off.numel()) - 1, n_tr_ids, cell_off,
-             alignment, alphas.ctypes.data, int(max_gt), int(max_tr), gt_partner, gt_level, tr_partner, tr_level,
-             matches, status], spare)
+    E._launch("clipops_hota_events_f64", sim.device,
+              [sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, frame_seq, int(gt_off.numel()) - 1, n_tr_ids, cell_off,
+               alignment, alphas.ctypes.data, int(max_gt), int(max_tr), gt_partner, gt_level, tr_partner, tr_level,
+               matches, status], spare)
 
 
 def launch_identity_pairs(n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, id_matches, max_ids: int,
                           gt_id_partner, gt_idtp, tr_id_partner, tr_idtp, status, spare=None) -> None:
     """``clipops_identity_pairs_i32`` on the current stream; the five outputs are written whole."""
-    _launch("clipops_identity_pairs_i32", n_gt_ids.device,
-            [int(n_gt_ids.numel()), n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, id_matches,
-             int(max_ids), gt_id_partner, gt_idtp, tr_id_partner, tr_idtp, status], spare)
+    E._launch("clipops_identity_pairs_i32", n_gt_ids.device,
+              [int(n_gt_ids.numel()), n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, id_matches,
+               int(max_ids), gt_id_partner, gt_idtp, tr_id_partner, tr_idtp, status], spare)
 
 
 def launch_assoc_reduce(n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, matches, max_side_ids: int,
                         alpha_index: int, gt_tp, gt_num, gt_top, tr_tp, tr_num, tr_top, spare=None) -> None:
     """``clipops_assoc_reduce_f64`` on the current stream; the six outputs are written whole."""
-    _launch("clipops_assoc_reduce_f64", n_gt_ids.device,
-            [int(n_gt_ids.numel()), n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, matches,
-             int(max_side_ids), int(alpha_index), gt_tp, gt_num, gt_top, tr_tp, tr_num, tr_top], spare)
+    E._launch("clipops_assoc_reduce_f64", n_gt_ids.device,
+              [int(n_gt_ids.numel()), n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, matches,
+               int(max_side_ids), int(alpha_index), gt_tp, gt_num, gt_top, tr_tp, tr_num, tr_top], spare)
 
 
 def launch_timeline(gt_off, gt_ids, partner_id, level, n_ids: int, alpha_index: int, cell_w: int, cell_h: int, bgr: bool,
                     image, spare=None) -> None:
     """``clipops_timeline_u8`` on the current stream, into ``image`` uint8 (n_ids * cell_h, F * cell_w, 3)."""
-    _launch("clipops_timeline_u8", image.device,
-            [gt_off, gt_ids, partner_id, level, int(n_ids), int(gt_off.numel()) - 1, int(alpha_index), int(cell_w),
-             int(cell_h), int(bool(bgr)), image], spare)
+    E._launch("clipops_timeline_u8", image.device,
+              [gt_off, gt_ids, partner_id, level, int(n_ids), int(gt_off.numel()) - 1, int(alpha_index), int(cell_w),
+               int(cell_h), int(bool(bgr)), image], spare)
 
 
 def device_association_tables(packed: E.PackedSequences, benchmark: str = "MOT17",
                               alpha_index: int = DEFAULT_ALPHA_INDEX, timings: dict = None) -> dict:
-    """``association_host``'s arrays by the kernels, as torch tensors on ``packed``'s device.  The front is the one
-    ``diagnose._device_rows`` and ``evaluation.device_tables`` state -- similarity, preprocessing match, compaction (the
-    same library calls on the same arrays) -- then ``trackeval_accumulate`` and the four launches of this module's
-    kernels, and the scatter to the input rows in index operations.  The front waits for the device where
-    ``diagnose``'s does (the compaction and the relabelling are the host's); behind it nothing waits: the status words of
-    the launches are returned as ``frame_status`` / ``id_status`` for ``raise_on_status`` once they are on the host.
-    ``timings``: a dict that receives, per call, a list of (start, end) event pairs (tools/bench_assoc.py)."""
+    """``association_host``'s arrays by the kernels, as torch tensors on ``packed``'s device:
+    ``evaluation.device_front`` and ``evaluation.device_accumulate``, then the four launches of this module's kernels,
+    and the scatter to the input rows in index operations.  The front waits for the device (the compaction and the
+    relabelling are the host's); behind it nothing waits: the status words of the launches are returned as
+    ``frame_status`` / ``id_status`` for ``raise_on_status`` once they are on the host.  ``timings``: a dict that
+    receives, per launch of this module's kernels, a list of (start, end) event pairs (tools/bench_assoc.py)."""
     import torch
-    from . import _track_eval_lib as L
-    dev = packed.gt_boxes.device
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)
-        ptr = lambda t: _ptr(t, nothing)                                           # noqa: E731
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)           # noqa: E731
-        new = lambda n, dt, fill=None: (torch.empty(max(int(n), 1), dtype=dt, device=dev) if fill is None else
-                                        torch.full((max(int(n), 1),), fill, dtype=dt, device=dev))     # noqa: E731
-
-        def timed(name, call):
-            if timings is None:
-                return call()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            call()
-            b.record()
-            timings.setdefault(name, []).append((a, b))
-
-        seq_off, gt_off, tr_off = (getattr(packed, k).cpu().numpy() for k in ("seq_off", "gt_off", "tr_off"))
-        S, F = len(seq_off) - 1, len(gt_off) - 1
-        tens = {k: getattr(packed, k).contiguous() for k in E.PackedSequences.ARRAYS}
-        frame_max = lambda off: int(np.diff(off).max()) if F else 0                # noqa: E731
-
-        def similarity(gt_boxes, tr_boxes, g_off, t_off):
-            s_off = E._sim_offsets(g_off, t_off)
-            sim = new(s_off[-1], torch.float64)
-            offs = up(g_off), up(t_off), up(s_off)
-            L.check(L.lib.trackeval_similarity(ptr(gt_boxes), ptr(tr_boxes), ptr(offs[0]), ptr(offs[1]), ptr(offs[2]),
-                                               F, ptr(sim), st), "trackeval_similarity")
-            return sim, offs
-
-        raw_sim, (d_gt_off, d_tr_off, d_sim_off) = similarity(tens["gt_boxes"], tens["tr_boxes"], gt_off, tr_off)
-        remove = new(tens["tr_ids"].numel(), torch.int32, 0)
-        if benchmark != "MOT15" and F:
-            status = new(F, torch.int32, 0)
-            L.check(L.lib.trackeval_preproc_match(ptr(raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off),
-                                                  ptr(tens["gt_classes"]), F, frame_max(gt_off), frame_max(tr_off),
-                                                  ptr(remove), ptr(status), st), "trackeval_preproc_match")
-            E._raise_on_status(status, "preprocessing match", "frame")
-        host = E.PackedSequences(packed.names, seq_off, gt_off, tr_off, None, None, tens["gt_ids"].cpu().numpy(),
-                                 tens["tr_ids"].cpu().numpy(), tens["gt_classes"].cpu().numpy(),
-                                 tens["gt_zero_marked"].cpu().numpy())
-        keep_gt = host.gt_zero_marked != 0
-        if benchmark != "MOT15":
-            keep_gt &= host.gt_classes == E.PEDESTRIAN
-        d = E._compact(host, keep_gt, remove[:tens["tr_ids"].numel()].cpu().numpy() == 0)
-        gt_boxes = tens["gt_boxes"][up(d["keep_gt"])].contiguous()
-        tr_boxes = tens["tr_boxes"][up(d["keep_tr"])].contiguous()
-        max_gt, max_tr = frame_max(d["gt_off"]), frame_max(d["tr_off"])
-        max_ids = int((d["n_gt_ids"] + d["n_tr_ids"]).max()) if S else 0
-        max_side = int(max(d["n_gt_ids"].max(), d["n_tr_ids"].max())) if S else 0
-        if max_ids > L.MAX_DIM:
-            raise ValueError(f"a sequence has {max_ids} ground-truth plus tracker ids: the identity assignment exceeds "
-                             f"the device limit of {L.MAX_DIM} (analyse it on the host)")
-        sim, (d_gt_off, d_tr_off, d_sim_off) = similarity(gt_boxes, tr_boxes, d["gt_off"], d["tr_off"])
-        gt_ids, tr_ids, d_seq_off = up(d["gt_ids"]), up(d["tr_ids"]), up(seq_off)
-        n_gt_ids, n_tr_ids = up(d["n_gt_ids"]), up(d["n_tr_ids"])
-        cell_off, gid_off, tid_off = up(d["cell_off"]), up(d["gid_off"]), up(d["tid_off"])
-        frame_seq = up(np.repeat(np.arange(S, dtype=np.int32), np.diff(seq_off)))
-        cells, n_gid, n_tid = int(d["cell_off"][-1]), int(d["gid_off"][-1]), int(d["tid_off"][-1])
-        n_gt, n_tr = len(d["gt_ids"]), len(d["tr_ids"])
-        potential, alignment = new(cells, torch.float64), new(cells, torch.float64)
-        id_matches, gt_count, tr_count = new(cells, torch.int32), new(n_gid, torch.int32), new(n_tid, torch.int32)
-        if S:
-            L.check(L.lib.trackeval_accumulate(ptr(sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(gt_ids),
-                                               ptr(tr_ids), ptr(d_seq_off), S, ptr(n_gt_ids), ptr(n_tr_ids),
-                                               ptr(cell_off), ptr(gid_off), ptr(tid_off), max_gt, max_tr, ptr(potential),
-                                               ptr(id_matches), ptr(gt_count), ptr(tr_count), ptr(alignment), st),
-                    "trackeval_accumulate")
+    with E._on_stream(packed.gt_boxes.device):
+        fr = E.device_front(packed, benchmark, on_host="analyse")
+        acc = E.device_accumulate(fr)
+        S, F, dev, new, timed = fr.S, fr.F, fr.dev, fr.new, E._timed(timings)
+        n_gt, n_tr, n_gid, n_tid, cells = len(fr.d["gt_ids"]), len(fr.d["tr_ids"]), fr.n_gid, fr.n_tid, fr.cells
         ev = {"gt_partner": new(n_gt, torch.int32), "gt_level": new(n_gt, torch.int32),
               "tr_partner": new(n_tr, torch.int32), "tr_level": new(n_tr, torch.int32)}
         matches = new(N_ALPHA * cells, torch.int32, 0)
@@ -542,26 +459,25 @@ def device_association_tables(packed: E.PackedSequences, benchmark: str = "MOT17
                   "tr_num": torch.empty((max(n_tid, 1), 2, N_ALPHA), dtype=torch.float64, device=dev),
                   "tr_top": torch.empty((max(n_tid, 1), 3), dtype=torch.int32, device=dev)}
         if F:
-            timed("clipops_hota_events_f64", lambda: launch_hota_events(
-                sim, d_sim_off, d_gt_off, d_tr_off, gt_ids, tr_ids, frame_seq, n_tr_ids, cell_off, alignment, max_gt,
-                max_tr, ev["gt_partner"], ev["gt_level"], ev["tr_partner"], ev["tr_level"], matches, frame_status, nothing))
+            timed("clipops_hota_events_f64", launch_hota_events, fr.sim, fr.sim_off, fr.gt_off, fr.tr_off, fr.gt_ids,
+                  fr.tr_ids, fr.frame_seq, fr.n_tr_ids, fr.cell_off, acc["alignment"], fr.max_gt, fr.max_tr,
+                  ev["gt_partner"], ev["gt_level"], ev["tr_partner"], ev["tr_level"], matches, frame_status, fr.spare)
         if S:
-            timed("clipops_identity_pairs_i32", lambda: launch_identity_pairs(
-                n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, id_matches, max_ids,
-                ids["gt_id_partner"], ids["gt_idtp"], ids["tr_id_partner"], ids["tr_idtp"], id_status, nothing))
-            timed("clipops_assoc_reduce_f64", lambda: launch_assoc_reduce(
-                n_gt_ids, n_tr_ids, cell_off, gid_off, tid_off, gt_count, tr_count, matches, max_side, alpha_index,
-                tables["gt_tp"], tables["gt_num"], tables["gt_top"], tables["tr_tp"], tables["tr_num"],
-                tables["tr_top"], nothing))
+            timed("clipops_identity_pairs_i32", launch_identity_pairs, fr.n_gt_ids, fr.n_tr_ids, fr.cell_off,
+                  fr.gid_off, fr.tid_off, acc["gt_count"], acc["tr_count"], acc["id_matches"], fr.max_ids,
+                  ids["gt_id_partner"], ids["gt_idtp"], ids["tr_id_partner"], ids["tr_idtp"], id_status, fr.spare)
+            timed("clipops_assoc_reduce_f64", launch_assoc_reduce, fr.n_gt_ids, fr.n_tr_ids, fr.cell_off, fr.gid_off,
+                  fr.tid_off, acc["gt_count"], acc["tr_count"], matches, fr.max_side, alpha_index, tables["gt_tp"],
+                  tables["gt_num"], tables["gt_top"], tables["tr_tp"], tables["tr_num"], tables["tr_top"], fr.spare)
         ev = {"gt_partner": ev["gt_partner"][:n_gt], "gt_level": ev["gt_level"][:n_gt],
               "tr_partner": ev["tr_partner"][:n_tr], "tr_level": ev["tr_level"][:n_tr]}
-        out = _to_input_rows(tens["gt_ids"], tens["tr_ids"], gt_off, tr_off, d, ev, sim)
-        out.update({"gt_count": gt_count[:n_gid], "tr_count": tr_count[:n_tid], "matches": matches[:N_ALPHA * cells]})
+        out = _to_input_rows(fr.tens["gt_ids"], fr.tens["tr_ids"], fr.host.gt_off, fr.host.tr_off, fr.d, ev, fr.sim)
+        out.update({"gt_count": acc["gt_count"][:n_gid], "tr_count": acc["tr_count"][:n_tid],
+                    "matches": matches[:N_ALPHA * cells]})
         out.update({k: v[:n_gid if k.startswith("gt") else n_tid] for k, v in list(ids.items()) + list(tables.items())})
         out.update({"c::" + k: v for k, v in ev.items()})
-        out["frame_status"] = frame_status[:F] if F else frame_status[:0]
-        out["id_status"] = id_status[:S] if S else id_status[:0]
-        out["host"] = _identity_tables(host, d)
+        out["frame_status"], out["id_status"] = frame_status[:F], id_status[:S]
+        out["host"] = _identity_tables(fr.host, fr.d)
         return out
 
 

@@ -17,9 +17,9 @@ Frames are numbered from 1 wherever this module names one (``switches``, ``worst
 
 The definition is stated twice, like the evaluation's.  ``clear_events_host`` walks every sequence as
 ``evaluation._clear_host`` does, after ``evaluation._preprocess_host``, and keeps what that walk decides per row; it is
-numpy and scipy.  With a CUDA ``device`` the similarity, the preprocessing match and the compaction run as
-``evaluation.device_tables`` runs them and ``clipops_clear_events_f64`` (memotr_amd/csrc/clip_tracks.h) walks the
-sequences, one wavefront each; integer results and similarities agree exactly.  The draw table is
+numpy and scipy.  With a CUDA ``device`` the similarity, the preprocessing match and the compaction are
+``evaluation.device_front``'s, the calls ``evaluation.device_tables`` stands on, and ``clipops_clear_events_f64``
+(memotr_amd/csrc/clip_tracks.h) walks the sequences, one wavefront each; integer results and similarities agree exactly.  The draw table is
 ``error_table_host`` -- ``render.track_table``'s rows with the colour of the event -- or ``clipops_error_table_f64``,
 word for word the same.
 
@@ -290,99 +290,49 @@ def _check_benchmark(benchmark: str) -> None:
 
 
 # ------------------------------------------------------------------------------------------------ the device path
-def _ptr(t, nothing):
-    return t.data_ptr() if t.numel() else nothing.data_ptr()
-
-
 def launch_clear_events(sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, seq_off, n_gt_ids, max_gt: int, max_tr: int,
                         max_gt_ids: int, gt_partner, gt_flags, tr_partner, counts, status) -> None:
     """``clipops_clear_events_f64`` on the current stream: contiguous CUDA tensors with the dtypes of
     include/clip_ops_hip.h; the five outputs are written whole, nothing waits."""
-    import torch
-    from . import _clip_lib as C
-    dev = seq_off.device
-    with torch.cuda.device(dev):
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)                  # an empty array's address
-        args = [_ptr(t, nothing) for t in (sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, seq_off)]
-        outs = [_ptr(t, nothing) for t in (gt_partner, gt_flags, tr_partner, counts, status)]
-        C.check(C.lib.clipops_clear_events_f64(*args, int(seq_off.numel()) - 1, _ptr(n_gt_ids, nothing), int(max_gt),
-                                               int(max_tr), int(max_gt_ids), *outs,
-                                               torch.cuda.current_stream(dev).cuda_stream), "clipops_clear_events_f64")
+    E._launch("clipops_clear_events_f64", seq_off.device,
+              [sim, sim_off, gt_off, tr_off, gt_ids, tr_ids, seq_off, int(seq_off.numel()) - 1, n_gt_ids, int(max_gt),
+               int(max_tr), int(max_gt_ids), gt_partner, gt_flags, tr_partner, counts, status])
 
 
 def launch_error_table(gt_boxes, tr_boxes, gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind, max_rows: int, width: int,
                        height: int, bgr: bool, font_scale: int, table) -> None:
     """``clipops_error_table_f64`` on the current stream, into ``table`` int32 (F, max_rows, 16)."""
+    E._launch("clipops_error_table_f64", table.device,
+              [gt_boxes, tr_boxes, gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind, int(gt_off.numel()) - 1,
+               int(max_rows), int(width), int(height), int(bool(bgr)), int(font_scale), table])
+
+
+def _walk_device(fr: E.DeviceFront, sequence: str = "sequence", run=None):
+    """``_walk_host`` over a front's sequences by one launch of ``clipops_clear_events_f64`` through the per-call hook
+    ``run``: (the walk's arrays, ``counts`` int32 [S, 5]).  ``sequence``: what an error calls one."""
     import torch
-    from . import _clip_lib as C
-    dev = table.device
-    with torch.cuda.device(dev):
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)
-        args = [_ptr(t, nothing) for t in (gt_boxes, tr_boxes, gt_off, tr_off, gt_ids, tr_ids, gt_kind, tr_kind)]
-        C.check(C.lib.clipops_error_table_f64(*args, int(gt_off.numel()) - 1, int(max_rows), int(width), int(height),
-                                              int(bool(bgr)), int(font_scale), _ptr(table, nothing),
-                                              torch.cuda.current_stream(dev).cuda_stream), "clipops_error_table_f64")
+    S, n_gt, n_tr = fr.S, len(fr.d["gt_ids"]), len(fr.d["tr_ids"])
+    walk = {"gt_partner": fr.new(n_gt, torch.int32), "gt_flags": fr.new(n_gt, torch.int32),
+            "tr_partner": fr.new(n_tr, torch.int32)}
+    counts, status = torch.empty((max(S, 1), 5), dtype=torch.int32, device=fr.dev), fr.new(S, torch.int32)
+    if S:
+        (run or fr.run)("clipops_clear_events_f64", launch_clear_events, fr.sim, fr.sim_off, fr.gt_off, fr.tr_off,
+                        fr.gt_ids, fr.tr_ids, fr.seq_off, fr.n_gt_ids, fr.max_gt, fr.max_tr, fr.max_gt_ids,
+                        walk["gt_partner"], walk["gt_flags"], walk["tr_partner"], counts, status)
+        E._raise_on_status(status[:S], "CLEAR events", sequence)
+    return {"gt_partner": walk["gt_partner"][:n_gt], "gt_flags": walk["gt_flags"][:n_gt],
+            "tr_partner": walk["tr_partner"][:n_tr]}, counts[:S]
 
 
 def _device_rows(packed: E.PackedSequences, benchmark: str) -> dict:
-    """``clear_events_host``'s arrays by the kernels, as torch tensors on ``packed``'s device: the similarity, the
-    preprocessing match and the compaction as ``evaluation.device_tables`` does them (the same library calls on the same
-    arrays), then one launch of ``clipops_clear_events_f64``."""
-    import torch
-    from . import _track_eval_lib as L
-    dev = packed.gt_boxes.device
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)
-        ptr = lambda t: _ptr(t, nothing)                                           # noqa: E731
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)           # noqa: E731
-        new = lambda n, dt, fill=None: (torch.empty(max(int(n), 1), dtype=dt, device=dev) if fill is None else
-                                        torch.full((max(int(n), 1),), fill, dtype=dt, device=dev))     # noqa: E731
-        seq_off, gt_off, tr_off = (getattr(packed, k).cpu().numpy() for k in ("seq_off", "gt_off", "tr_off"))
-        S, F = len(seq_off) - 1, len(gt_off) - 1
-        tens = {k: getattr(packed, k).contiguous() for k in E.PackedSequences.ARRAYS}
-        frame_max = lambda off: int(np.diff(off).max()) if F else 0                # noqa: E731
-
-        def similarity(gt_boxes, tr_boxes, g_off, t_off):
-            s_off = E._sim_offsets(g_off, t_off)
-            sim = new(s_off[-1], torch.float64)
-            offs = up(g_off), up(t_off), up(s_off)
-            L.check(L.lib.trackeval_similarity(ptr(gt_boxes), ptr(tr_boxes), ptr(offs[0]), ptr(offs[1]), ptr(offs[2]),
-                                               F, ptr(sim), st), "trackeval_similarity")
-            return sim, offs
-
-        raw_sim, (d_gt_off, d_tr_off, d_sim_off) = similarity(tens["gt_boxes"], tens["tr_boxes"], gt_off, tr_off)
-        remove = new(tens["tr_ids"].numel(), torch.int32, 0)
-        if benchmark != "MOT15" and F:
-            status = new(F, torch.int32, 0)
-            L.check(L.lib.trackeval_preproc_match(ptr(raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off),
-                                                  ptr(tens["gt_classes"]), F, frame_max(gt_off), frame_max(tr_off),
-                                                  ptr(remove), ptr(status), st), "trackeval_preproc_match")
-            E._raise_on_status(status, "preprocessing match", "frame")
-        host = E.PackedSequences(packed.names, seq_off, gt_off, tr_off, None, None, tens["gt_ids"].cpu().numpy(),
-                                 tens["tr_ids"].cpu().numpy(), tens["gt_classes"].cpu().numpy(),
-                                 tens["gt_zero_marked"].cpu().numpy())
-        keep_gt = host.gt_zero_marked != 0
-        if benchmark != "MOT15":
-            keep_gt &= host.gt_classes == E.PEDESTRIAN
-        d = E._compact(host, keep_gt, remove[:tens["tr_ids"].numel()].cpu().numpy() == 0)
-        gt_boxes = tens["gt_boxes"][up(d["keep_gt"])].contiguous()
-        tr_boxes = tens["tr_boxes"][up(d["keep_tr"])].contiguous()
-        sim, (d_gt_off, d_tr_off, d_sim_off) = similarity(gt_boxes, tr_boxes, d["gt_off"], d["tr_off"])
-        n_gt, n_tr = len(d["gt_ids"]), len(d["tr_ids"])
-        walk = {"gt_partner": new(n_gt, torch.int32), "gt_flags": new(n_gt, torch.int32),
-                "tr_partner": new(n_tr, torch.int32)}
-        counts, status = torch.empty((max(S, 1), 5), dtype=torch.int32, device=dev), new(S, torch.int32)
-        if S:
-            launch_clear_events(sim, d_sim_off, d_gt_off, d_tr_off, up(d["gt_ids"]), up(d["tr_ids"]), up(seq_off),
-                                up(d["n_gt_ids"]), frame_max(d["gt_off"]), frame_max(d["tr_off"]),
-                                int(d["n_gt_ids"].max()), walk["gt_partner"], walk["gt_flags"], walk["tr_partner"],
-                                counts, status)
-            E._raise_on_status(status[:S], "CLEAR events", "sequence")
-        walk = {"gt_partner": walk["gt_partner"][:n_gt], "gt_flags": walk["gt_flags"][:n_gt],
-                "tr_partner": walk["tr_partner"][:n_tr]}
-        rows = _to_input_rows(host, d, walk, sim)
-        rows["counts"] = counts[:S]
+    """``clear_events_host``'s arrays by the kernels, as torch tensors on ``packed``'s device: ``evaluation.device_front``
+    (no launch here solves an identity assignment, so none is checked), then one launch of
+    ``clipops_clear_events_f64``."""
+    with E._on_stream(packed.gt_boxes.device):
+        fr = E.device_front(packed, benchmark)
+        walk, counts = _walk_device(fr)
+        rows = _to_input_rows(fr.host, fr.d, walk, fr.sim)
+        rows["counts"] = counts
         return rows
 
 

@@ -39,8 +39,8 @@ rows without a cross partner.  Row g sums to the ground-truth detections of clas
 detections of class t.
 
 The definition is stated twice.  ``bdd_events_host`` is numpy and scipy.  With a CUDA ``device`` the class split, the
-similarity and the preprocessing run as ``device_tables_bdd`` runs them (the same library calls on the same arrays;
-the split carries row numbers in place of ids, which gives the source row of every split row), ONE launch of
+similarity and the preprocessing are ``evaluation_bdd100k.device_front_bdd``'s, the calls ``device_tables_bdd`` stands on
+(here the split carries row numbers in place of ids, which gives the source row of every split row), ONE launch of
 ``clipops_clear_events_f64`` walks the S * 8 problems, and ``clipops_bdd_cross_class_f64`` (memotr_amd/csrc/clip_tracks.h)
 pairs every frame, one wavefront each; the confusion matrix is an integer ``bincount``.  Integer results and IoUs agree
 with the host statement exactly.
@@ -389,114 +389,30 @@ def launch_cross_class(gt_boxes, tr_boxes, gt_classes, tr_classes, gt_off, tr_of
                        max_tr: int, gt_partner, gt_class, gt_iou, tr_partner, tr_class, tr_iou, status) -> None:
     """``clipops_bdd_cross_class_f64`` on the current stream: contiguous CUDA tensors with the dtypes of
     include/clip_ops_hip.h; the seven outputs are written whole, nothing waits."""
-    import torch
-    from . import _clip_lib as C
-    dev = gt_off.device
-    with torch.cuda.device(dev):
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)                  # an empty array's address
-        args = [D._ptr(t, nothing) for t in (gt_boxes, tr_boxes, gt_classes, tr_classes, gt_off, tr_off, gt_kind, tr_kind)]
-        outs = [D._ptr(t, nothing) for t in (gt_partner, gt_class, gt_iou, tr_partner, tr_class, tr_iou, status)]
-        C.check(C.lib.clipops_bdd_cross_class_f64(*args, int(gt_off.numel()) - 1, int(max_gt), int(max_tr), *outs,
-                                                  torch.cuda.current_stream(dev).cuda_stream),
-                "clipops_bdd_cross_class_f64")
+    E._launch("clipops_bdd_cross_class_f64", gt_off.device,
+              [gt_boxes, tr_boxes, gt_classes, tr_classes, gt_off, tr_off, gt_kind, tr_kind, int(gt_off.numel()) - 1,
+               int(max_gt), int(max_tr), gt_partner, gt_class, gt_iou, tr_partner, tr_class, tr_iou, status])
 
 
 def _device_rows(packed: B.PackedBDD, timings: dict = None) -> dict:
-    """``bdd_events_host``'s arrays by the kernels, as torch tensors on ``packed``'s device, on the current stream.  Up to
-    the compaction this is ``device_tables_bdd`` call for call, with one difference that changes no result: the class
-    split scatters the rows' own numbers where that function scatters their ids, so its output is ``gt_src`` /
-    ``tr_src`` and the split ids are one gather through it.  ``timings``: a dictionary that receives a pair of HIP
-    events around each of the two launches of this module (tools/bench_bdd_events.py)."""
+    """``bdd_events_host``'s arrays by the kernels, as torch tensors on ``packed``'s device, on the current stream:
+    ``evaluation_bdd100k.device_front_bdd`` with the class split carrying row numbers, ONE launch of
+    ``clipops_clear_events_f64`` over the S * 8 problems (``diagnose._walk_device``), the scatter to the input rows,
+    ``clipops_bdd_cross_class_f64`` over the input frames and the confusion matrix from integers.  ``timings``: a
+    dictionary that receives a pair of HIP events around each of the two launches of this module
+    (tools/bench_bdd_events.py)."""
     import torch
-    from . import _track_eval_bdd_lib as L
-    dev = packed.gt_boxes.device
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)
-        ptr = lambda t: D._ptr(t, nothing)                                         # noqa: E731
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)           # noqa: E731
-        new = lambda n, dt, fill=None: (torch.empty(max(int(n), 1), dtype=dt, device=dev) if fill is None else
-                                        torch.full((max(int(n), 1),), fill, dtype=dt, device=dev))     # noqa: E731
-        seq_off, in_gt_off, in_tr_off = (getattr(packed, k).cpu().numpy() for k in ("seq_off", "gt_off", "tr_off"))
-        S, F = len(seq_off) - 1, len(in_gt_off) - 1
-        P, F8 = S * N_CLASSES, F * N_CLASSES
-        tens = {k: getattr(packed, k).contiguous() for k in B.PackedBDD.ARRAYS}
-        NG, NT = tens["gt_ids"].numel(), tens["tr_ids"].numel()
-        split_seq_off, frame_src = B._split_offsets(seq_off)
-        frame_seq = up(np.repeat(np.arange(S, dtype=np.int32), np.diff(seq_off)))
-        frame_max = lambda off: int(np.diff(off).max()) if len(off) > 1 else 0     # noqa: E731
-
-        def timed(name, launch, *args):
-            if timings is None:
-                return launch(*args)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            launch(*args)
-            b.record()
-            timings.setdefault(name, []).append((a, b))
-
-        # 1. the class split, carrying row numbers
-        counts = torch.zeros((2, max(F8, 1)), dtype=torch.int32, device=dev)
-        if F:
-            L.check(L.lib.bddeval_class_count(ptr(tens["gt_classes"]), ptr(tens["tr_classes"]), ptr(tens["gt_off"]),
-                                              ptr(tens["tr_off"]), ptr(tens["seq_off"]), ptr(frame_seq), F,
-                                              ptr(counts[0]), ptr(counts[1]), st), "bddeval_class_count")
-        offs = torch.zeros((2, F8 + 1), dtype=torch.int32, device=dev)
-        offs[:, 1:] = torch.cumsum(counts[:, :F8], 1, dtype=torch.int32)
-        d_gt_off, d_tr_off = offs[0].contiguous(), offs[1].contiguous()
-        gt_off, tr_off = d_gt_off.cpu().numpy(), d_tr_off.cpu().numpy()            # (synchronises: sizes the rest)
-        n_gt, n_tr = int(gt_off[-1]), int(tr_off[-1])
-        gt_boxes, tr_boxes = new(4 * n_gt, torch.float64), new(4 * n_tr, torch.float64)
-        gt_src, tr_src = new(n_gt, torch.int32), new(n_tr, torch.int32)
-        if F:
-            row_numbers = torch.arange(max(NG, NT, 1), dtype=torch.int32, device=dev)
-            L.check(L.lib.bddeval_class_split(ptr(tens["gt_boxes"]), ptr(tens["tr_boxes"]), ptr(row_numbers),
-                                              ptr(row_numbers), ptr(tens["gt_classes"]), ptr(tens["tr_classes"]),
-                                              ptr(tens["gt_off"]), ptr(tens["tr_off"]), ptr(tens["seq_off"]),
-                                              ptr(frame_seq), F, ptr(d_gt_off), ptr(d_tr_off), ptr(gt_boxes),
-                                              ptr(tr_boxes), ptr(gt_src), ptr(tr_src), st), "bddeval_class_split")
-        gt_src, tr_src = gt_src[:n_gt].long(), tr_src[:n_tr].long()
-        gt_ids, tr_ids = tens["gt_ids"][gt_src], tens["tr_ids"][tr_src]
-
-        def similarity(g_boxes, t_boxes, g_off, t_off):
-            s_off = E._sim_offsets(g_off, t_off)
-            sim = new(s_off[-1], torch.float64)
-            offsets = up(g_off), up(t_off), up(s_off)
-            L.check(L.lib.bddeval_similarity(ptr(g_boxes), ptr(t_boxes), ptr(offsets[0]), ptr(offsets[1]),
-                                             ptr(offsets[2]), F8, ptr(sim), st), "bddeval_similarity")
-            return sim, offsets
-
-        # 2. raw similarity; one assignment per (frame, class), then the ignore regions for what stayed unmatched
-        raw_sim, (_, _, d_sim_off) = similarity(gt_boxes, tr_boxes, gt_off, tr_off)
-        remove = new(n_tr, torch.int32, 0)
-        if F8:
-            status = new(F8, torch.int32, 0)
-            L.check(L.lib.bddeval_preproc(ptr(raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(tr_boxes),
-                                          ptr(tens["ig_off"]), ptr(tens["ig_boxes"]), ptr(up(frame_src)), F8,
-                                          frame_max(gt_off), frame_max(tr_off), ptr(remove), ptr(status), st),
-                    "bddeval_preproc")
-            E._raise_on_status(status, "preprocessing match", "(frame, class)")
-        # 3. the filter and the relabelling, on the host (small integer arrays; not hot)
-        host = E.PackedSequences([f"{n}/{c}" for n in packed.names for c in CLASSES], split_seq_off, gt_off, tr_off,
-                                 None, None, gt_ids.cpu().numpy(), tr_ids.cpu().numpy(), None, None)
-        d = E._compact(host, np.ones(n_gt, bool), remove[:n_tr].cpu().numpy() == 0)
-        kept_boxes = tr_boxes[:4 * n_tr].view(-1, 4)[up(d["keep_tr"])].contiguous()
-        sim, (k_gt_off, k_tr_off, k_sim_off) = similarity(gt_boxes, kept_boxes, d["gt_off"], d["tr_off"])
-        # 4. one walk over the S * 8 problems
-        k_gt, k_tr = len(d["gt_ids"]), len(d["tr_ids"])
-        walk = {"gt_partner": new(k_gt, torch.int32), "gt_flags": new(k_gt, torch.int32),
-                "tr_partner": new(k_tr, torch.int32)}
-        counts, status = torch.empty((max(P, 1), 5), dtype=torch.int32, device=dev), new(P, torch.int32)
-        if P:
-            timed("clipops_clear_events_f64", D.launch_clear_events, sim, k_sim_off, k_gt_off, k_tr_off,
-                  up(d["gt_ids"]), up(d["tr_ids"]), up(split_seq_off), up(d["n_gt_ids"]), frame_max(d["gt_off"]), frame_max(d["tr_off"]),
-                  int(d["n_gt_ids"].max()), walk["gt_partner"], walk["gt_flags"], walk["tr_partner"], counts, status)
-            E._raise_on_status(status[:P], "CLEAR events", "(sequence, class)")
-        walk = {"gt_partner": walk["gt_partner"][:k_gt], "gt_flags": walk["gt_flags"][:k_gt],
-                "tr_partner": walk["tr_partner"][:k_tr]}
-        split = {"gt_off": gt_off, "tr_off": tr_off, "gt_src": gt_src, "tr_src": tr_src, "frame_src": frame_src}
-        rows = _rows_from_split(in_gt_off, in_tr_off, split, D._to_input_rows(host, d, walk, sim))
-        # 5. the cross-class pairs of every input frame, and the confusion matrix from integers
+    with E._on_stream(packed.gt_boxes.device):
+        fr = B.device_front_bdd(packed, scatter_rows=True)
+        tens, new, up, timed = fr.tens, fr.new, fr.up, E._timed(timings)
+        seq_off, in_gt_off, in_tr_off = fr.split["seq_off"], tens["gt_off"].cpu().numpy(), tens["tr_off"].cpu().numpy()
+        S, F, NG, NT = len(seq_off) - 1, len(in_gt_off) - 1, tens["gt_ids"].numel(), tens["tr_ids"].numel()
+        # one walk over the S * 8 problems
+        walk, counts = D._walk_device(fr, "(sequence, class)", timed)
+        split = {"gt_off": fr.host.gt_off, "tr_off": fr.host.tr_off, "gt_src": fr.split["gt_src"],
+                 "tr_src": fr.split["tr_src"], "frame_src": fr.split["frame_src"]}
+        rows = _rows_from_split(in_gt_off, in_tr_off, split, D._to_input_rows(fr.host, fr.d, walk, fr.sim))
+        # the cross-class pairs of every input frame, and the confusion matrix from integers
         cross = {"gt_cross_partner": new(NG, torch.int32), "gt_cross_class": new(NG, torch.int32),
                  "gt_cross_iou": new(NG, torch.float64), "tr_cross_partner": new(NT, torch.int32),
                  "tr_cross_class": new(NT, torch.int32), "tr_cross_iou": new(NT, torch.float64)}
@@ -504,8 +420,8 @@ def _device_rows(packed: B.PackedBDD, timings: dict = None) -> dict:
             status = new(F, torch.int32)
             timed("clipops_bdd_cross_class_f64", launch_cross_class, tens["gt_boxes"], tens["tr_boxes"],
                   tens["gt_classes"], tens["tr_classes"], tens["gt_off"], tens["tr_off"], rows["gt_kind"],
-                  rows["tr_kind"], min(frame_max(in_gt_off), CROSS_MAX_DIM), min(frame_max(in_tr_off), CROSS_MAX_DIM),
-                  *cross.values(), status)
+                  rows["tr_kind"], min(E._frame_max(in_gt_off), CROSS_MAX_DIM),
+                  min(E._frame_max(in_tr_off), CROSS_MAX_DIM), *cross.values(), status)
             over = (status[:F] == -2).nonzero()
             if over.numel():
                 f = int(over[0])
@@ -514,7 +430,7 @@ def _device_rows(packed: B.PackedBDD, timings: dict = None) -> dict:
                                  "cross-class candidates on a side exceed the device limit (analyse it on the host)")
             E._raise_on_status(status[:F], "cross-class match", "frame")
         rows.update({k: v[:NG if k.startswith("gt") else NT] for k, v in cross.items()})
-        rows["counts"] = counts[:P].reshape(S, N_CLASSES, 5)
+        rows["counts"] = counts.reshape(S, N_CLASSES, 5)
         rows["confusion"] = _confusion(S, up(_row_sequences(seq_off, in_gt_off)), class_index(tens["gt_classes"]).long(),
                                        rows["gt_kind"].long(), rows["gt_cross_class"].long(),
                                        up(_row_sequences(seq_off, in_tr_off)), class_index(tens["tr_classes"]).long(),

@@ -13,7 +13,8 @@ The definition is stated twice.  ``host_tables`` is numpy and ``scipy.optimize.l
 the definitions (Luiten et al., "HOTA", IJCV 2020; Bernardin & Stiefelhagen, CLEAR MOT, 2008; Ristani et al., ID
 measures, 2016, and the conventions of TrackEval's implementation of them: thresholds shifted by the float64 epsilon,
 the order of the matching, what an empty side returns).  ``device_tables`` is the same on the GPU
-(memotr_amd/csrc/track_eval.hip).  Both produce the per-sequence tables that ``_sequence_result`` turns into
+(memotr_amd/csrc/track_eval.hip): ``device_front`` preprocesses, and the metric stage, ``diagnose`` and ``association``
+stand on what it returns.  Both produce the per-sequence tables that ``_sequence_result`` turns into
 TrackEval's fields; integer fields and similarities agree exactly, float fields to float64 summation order.  The
 host statement is the default wherever the inputs live; the kernels run where a CUDA ``device`` is asked for, and a
 missing library raises then.  (The kernels become the default for device inputs once ``tools/bench_eval.py`` has shown
@@ -342,118 +343,242 @@ def host_tables(packed: PackedSequences, benchmark: str = "MOT17") -> dict:
 
 
 # ------------------------------------------------------------------------------------------------ the device path
+def _ptr(t, spare):
+    return t.data_ptr() if t.numel() else spare.data_ptr()
+
+
+def _call(module, name, *args):
+    module.check(getattr(module.lib, name)(*args), name)
+
+
+def _launch(name: str, dev, tensors_and_ints, spare=None) -> None:
+    """One entry point of libclip_ops_hip.so on the current stream of ``dev``: tensors become addresses (an empty one the
+    address of ``spare``, a two-word array the caller keeps; allocated here when there is none), ``None`` a null pointer,
+    everything else is passed as it is."""
+    import torch
+    from . import _clip_lib as C
+    with torch.cuda.device(dev):
+        if spare is None:
+            spare = torch.zeros(2, dtype=torch.float64, device=dev)
+        args = [_ptr(a, spare) if hasattr(a, "data_ptr") else a for a in tensors_and_ints]
+        _call(C, name, *args, torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _timed(timings: dict = None):
+    """The per-call hook of the device paths, ``run(name, fn, *args)``: ``fn(*args)``; with a dict, between a pair of
+    events that ``timings[name]`` receives."""
+    def run(name, fn, *args):
+        if timings is None:
+            return fn(*args)
+        import torch
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn(*args)
+        b.record()
+        timings.setdefault(name, []).append((a, b))
+    return run
+
+
+def _on_stream(dev, stream=None):
+    import torch
+    return torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev)
+
+
+def _most(a) -> int:
+    return int(a.max()) if len(a) else 0
+
+
+def _frame_max(off) -> int:
+    return _most(np.diff(off))
+
+
+class DeviceFront:
+    """What every device path starts from (``device_front``, ``evaluation_bdd100k.device_front_bdd``): the preprocessed
+    data on the host and on the device, and the helpers the launches behind it are written with.
+
+    Host: ``d`` (``_compact``'s dictionary), ``host`` (the ``PackedSequences`` it was made from), ``tens`` (the input's
+    tensors, contiguous), ``S`` sequences, ``F`` frames, ``cells`` / ``n_gid`` / ``n_tid`` (the lengths of the id-pair
+    and the per-id tables), and the launch sizes: ``max_gt`` / ``max_tr`` (kept detections of a frame), ``max_gt_ids`` /
+    ``max_side`` / ``max_ids`` (a sequence's ground-truth ids, ids on its larger side, ids of both sides).
+    Device: ``raw_sim`` [``n_raw``] of the input's frames; ``sim`` [``n_sim``] of the kept detections behind ``gt_off``,
+    ``tr_off``, ``sim_off``; the relabelled ``gt_ids``, ``tr_ids``; ``seq_off``, ``n_gt_ids``; and, once
+    ``device_accumulate`` has run, ``n_tr_ids``, ``cell_off``, ``gid_off``, ``tid_off``, ``frame_seq``.  Arrays a launch
+    writes are at least one element long."""
+
+    def __init__(self, dev, run=None):
+        import torch
+        self.dev, self.run = dev, run or _timed(None)
+        self.st = torch.cuda.current_stream(dev).cuda_stream
+        self.spare = torch.zeros(2, dtype=torch.float64, device=dev)                # an empty array's address
+
+    def ptr(self, t):
+        return _ptr(t, self.spare)
+
+    def up(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def new(self, n, dtype, fill=None):
+        import torch
+        if fill is None:
+            return torch.empty(max(int(n), 1), dtype=dtype, device=self.dev)
+        return torch.full((max(int(n), 1),), fill, dtype=dtype, device=self.dev)
+
+    def call(self, module, name, *args):
+        """``name`` of the library bound in ``module`` on the front's stream, through the per-call hook."""
+        self.run(name, _call, module, name, *args, self.st)
+
+    def similarity(self, entry, gt_boxes, tr_boxes, g_off, t_off):
+        """``entry``, a (module, name) pair with ``trackeval_similarity``'s arguments, over the frames behind the host
+        offsets: (similarity, the uploaded ground-truth, tracker and similarity offsets, the similarity's length)."""
+        import torch
+        s_off = _sim_offsets(g_off, t_off)
+        sim = self.new(s_off[-1], torch.float64)
+        offs = self.up(g_off), self.up(t_off), self.up(s_off)
+        self.call(*entry, self.ptr(gt_boxes), self.ptr(tr_boxes), self.ptr(offs[0]), self.ptr(offs[1]),
+                  self.ptr(offs[2]), len(g_off) - 1, self.ptr(sim))
+        return sim, offs, int(s_off[-1])
+
+
+def _front_tables(fr: DeviceFront, entry, host: PackedSequences, keep_gt, keep_tr, gt_boxes, tr_boxes,
+                  check_ids=None) -> DeviceFront:
+    """The second half of a front, from the keep masks on: ``_compact`` on the host (small integer arrays; not hot), the
+    kept boxes, their similarity by ``entry``, the relabelled ids on the device.  ``keep_gt`` None: all ground truth
+    stays and ``gt_boxes`` is taken as it is.  ``check_ids(ids per sequence)`` may raise before anything more is
+    launched."""
+    gather_gt = keep_gt is not None
+    fr.host, fr.d = host, _compact(host, keep_gt if gather_gt else np.ones(len(host.gt_ids), bool), keep_tr)
+    d, up = fr.d, fr.up
+    if gather_gt:
+        gt_boxes = gt_boxes[up(d["keep_gt"])].contiguous()
+    tr_boxes = tr_boxes[up(d["keep_tr"])].contiguous()
+    fr.S, fr.F = len(host.seq_off) - 1, len(host.gt_off) - 1
+    fr.max_gt, fr.max_tr = _frame_max(d["gt_off"]), _frame_max(d["tr_off"])
+    n_ids = d["n_gt_ids"].astype(np.int64) + d["n_tr_ids"]
+    fr.max_gt_ids, fr.max_side = _most(d["n_gt_ids"]), _most(np.maximum(d["n_gt_ids"], d["n_tr_ids"]))
+    fr.max_ids = _most(n_ids)
+    if check_ids is not None:
+        check_ids(n_ids)
+    fr.sim, (fr.gt_off, fr.tr_off, fr.sim_off), fr.n_sim = fr.similarity(entry, gt_boxes, tr_boxes, d["gt_off"],
+                                                                         d["tr_off"])
+    fr.gt_ids, fr.tr_ids = up(d["gt_ids"]), up(d["tr_ids"])
+    fr.seq_off, fr.n_gt_ids = up(host.seq_off), up(d["n_gt_ids"])
+    fr.cells, fr.n_gid, fr.n_tid = int(d["cell_off"][-1]), int(d["gid_off"][-1]), int(d["tid_off"][-1])
+    return fr
+
+
+def device_front(packed: PackedSequences, benchmark: str, run=None, on_host: str = None) -> DeviceFront:
+    """``_preprocess_host`` by the kernels of libtrack_eval_hip.so, on the current stream; ``packed`` holds CUDA tensors.
+    The one statement of what ``device_tables``, ``diagnose._device_rows`` and
+    ``association.device_association_tables`` start with: the raw similarity; under MOT17 rules one assignment per frame
+    that flags the detections on distractors (``trackeval_preproc_match``); the filters and the relabelling on the host,
+    which waits for the device; the similarity of what is kept.  ``run``: the per-call hook (``_timed``) every library
+    call goes through.  ``on_host``: what the caller's error advises ("evaluate", "analyse") for a sequence whose
+    identity assignment exceeds the device limit; None where no launch behind the front solves one."""
+    import torch
+    from . import _track_eval_lib as L
+    fr = DeviceFront(packed.gt_boxes.device, run)
+    ptr, entry = fr.ptr, (L, "trackeval_similarity")
+    seq_off, gt_off, tr_off = (getattr(packed, k).cpu().numpy() for k in ("seq_off", "gt_off", "tr_off"))
+    F = len(gt_off) - 1
+    fr.tens = tens = {k: getattr(packed, k).contiguous() for k in PackedSequences.ARRAYS}
+    fr.raw_sim, (d_gt_off, d_tr_off, d_sim_off), fr.n_raw = fr.similarity(entry, tens["gt_boxes"], tens["tr_boxes"],
+                                                                          gt_off, tr_off)
+    n_tr = tens["tr_ids"].numel()
+    remove = fr.new(n_tr, torch.int32, 0)
+    if benchmark != "MOT15" and F:
+        status = fr.new(F, torch.int32, 0)
+        fr.call(L, "trackeval_preproc_match", ptr(fr.raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off),
+                ptr(tens["gt_classes"]), F, _frame_max(gt_off), _frame_max(tr_off), ptr(remove), ptr(status))
+        _raise_on_status(status, "preprocessing match", "frame")
+    host = PackedSequences(packed.names, seq_off, gt_off, tr_off, None, None, tens["gt_ids"].cpu().numpy(),
+                           tens["tr_ids"].cpu().numpy(), tens["gt_classes"].cpu().numpy(),
+                           tens["gt_zero_marked"].cpu().numpy())
+    keep_gt = host.gt_zero_marked != 0
+    if benchmark != "MOT15":
+        keep_gt &= host.gt_classes == PEDESTRIAN
+
+    def check_ids(n_ids):
+        if on_host and _most(n_ids) > L.MAX_DIM:
+            raise ValueError(f"a sequence has {_most(n_ids)} ground-truth plus tracker ids: the identity assignment "
+                             f"exceeds the device limit of {L.MAX_DIM} ({on_host} it on the host)")
+
+    return _front_tables(fr, entry, host, keep_gt, remove[:n_tr].cpu().numpy() == 0, tens["gt_boxes"],
+                         tens["tr_boxes"], check_ids)
+
+
+def device_accumulate(fr: DeviceFront) -> dict:
+    """``trackeval_accumulate`` over a front's kept detections, with its set-up: the front gets the id tables on the
+    device (``n_tr_ids``, ``cell_off``, ``gid_off``, ``tid_off``, ``frame_seq``), which only the launches behind this one
+    read; returned are ``potential``, ``alignment`` float64 and ``id_matches`` int32 [cells], ``gt_count`` [n_gid],
+    ``tr_count`` [n_tid] int32.  Unguarded: with no sequence the entry point launches nothing, and the five arrays are
+    empty behind their one element."""
+    import torch
+    from . import _track_eval_lib as L
+    d, ptr, up = fr.d, fr.ptr, fr.up
+    fr.n_tr_ids = up(d["n_tr_ids"])
+    fr.cell_off, fr.gid_off, fr.tid_off = up(d["cell_off"]), up(d["gid_off"]), up(d["tid_off"])
+    fr.frame_seq = up(np.repeat(np.arange(fr.S, dtype=np.int32), np.diff(fr.host.seq_off)))
+    acc = {"potential": fr.new(fr.cells, torch.float64), "alignment": fr.new(fr.cells, torch.float64),
+           "id_matches": fr.new(fr.cells, torch.int32), "gt_count": fr.new(fr.n_gid, torch.int32),
+           "tr_count": fr.new(fr.n_tid, torch.int32)}
+    fr.call(L, "trackeval_accumulate", ptr(fr.sim), ptr(fr.sim_off), ptr(fr.gt_off), ptr(fr.tr_off), ptr(fr.gt_ids),
+            ptr(fr.tr_ids), ptr(fr.seq_off), fr.S, ptr(fr.n_gt_ids), ptr(fr.n_tr_ids), ptr(fr.cell_off),
+            ptr(fr.gid_off), ptr(fr.tid_off), fr.max_gt, fr.max_tr, ptr(acc["potential"]), ptr(acc["id_matches"]),
+            ptr(acc["gt_count"]), ptr(acc["tr_count"]), ptr(acc["alignment"]))
+    return acc
+
+
+def _metric_tables(fr: DeviceFront, frame: str = "frame", sequence: str = "sequence") -> dict:
+    """The metric stage behind a front, its ``S`` sequences being whatever the front made them (BDD100K's are
+    (sequence, class) pairs): accumulate, HOTA match and reduce, CLEAR, Identity; ``device_tables``' dictionary.
+    ``frame`` / ``sequence``: what an error calls them."""
+    import torch
+    from . import _track_eval_lib as L
+    S, F, dev, d, ptr, new = fr.S, fr.F, fr.dev, fr.d, fr.ptr, fr.new
+    n_alpha = len(ALPHAS)
+    acc = device_accumulate(fr)
+    matches = new(n_alpha * fr.cells, torch.int32, 0)
+    tp, loc = new(F * n_alpha, torch.int32), new(F * n_alpha, torch.float64)
+    frame_status = new(F, torch.int32, 0)
+    alphas = np.ascontiguousarray(ALPHAS, np.float64)
+    fr.call(L, "trackeval_hota_match", ptr(fr.sim), ptr(fr.sim_off), ptr(fr.gt_off), ptr(fr.tr_off), ptr(fr.gt_ids),
+            ptr(fr.tr_ids), ptr(fr.frame_seq), F, ptr(fr.n_tr_ids), ptr(fr.cell_off), ptr(acc["alignment"]),
+            alphas.ctypes.data, fr.max_gt, fr.max_tr, ptr(matches), ptr(tp), ptr(loc), ptr(frame_status))
+    hota_tp = torch.zeros((S, n_alpha), dtype=torch.int64, device=dev)
+    hota_sums = torch.zeros((S, 4, n_alpha), dtype=torch.float64, device=dev)
+    fr.call(L, "trackeval_hota_reduce", ptr(fr.seq_off), S, ptr(fr.n_gt_ids), ptr(fr.n_tr_ids), ptr(fr.cell_off),
+            ptr(fr.gid_off), ptr(fr.tid_off), ptr(acc["gt_count"]), ptr(acc["tr_count"]), ptr(matches), ptr(tp),
+            ptr(loc), ptr(hota_tp), ptr(hota_sums))
+    clear_ints = torch.zeros((S, 8), dtype=torch.int32, device=dev)
+    motp_sum = torch.zeros(S, dtype=torch.float64, device=dev)
+    clear_status, id_status = new(S, torch.int32, 0), new(S, torch.int32, 0)
+    fr.call(L, "trackeval_clear", ptr(fr.sim), ptr(fr.sim_off), ptr(fr.gt_off), ptr(fr.tr_off), ptr(fr.gt_ids),
+            ptr(fr.tr_ids), ptr(fr.seq_off), S, ptr(fr.n_gt_ids), fr.max_gt, fr.max_tr, fr.max_gt_ids,
+            ptr(clear_ints), ptr(motp_sum), ptr(clear_status))
+    identity = torch.zeros((S, 2), dtype=torch.int64, device=dev)
+    fr.call(L, "trackeval_identity", S, ptr(fr.n_gt_ids), ptr(fr.n_tr_ids), ptr(fr.cell_off), ptr(fr.gid_off),
+            ptr(fr.tid_off), ptr(acc["gt_count"]), ptr(acc["tr_count"]), ptr(acc["id_matches"]), fr.max_ids,
+            ptr(identity), ptr(id_status))
+    _raise_on_status(frame_status, "HOTA match", frame)
+    _raise_on_status(clear_status[:S], "CLEAR", sequence)
+    _raise_on_status(id_status[:S], "Identity", sequence)
+    return {"raw_similarity": fr.raw_sim[:fr.n_raw], "similarity": fr.sim[:fr.n_sim], "hota_tp": hota_tp,
+            "hota_sums": hota_sums, "clear_ints": clear_ints.long(), "motp_sum": motp_sum, "identity": identity,
+            "gt_off": fr.gt_off, "tr_off": fr.tr_off, "gt_ids": fr.gt_ids, "tr_ids": fr.tr_ids,
+            "n_gt_ids": fr.n_gt_ids, "n_tr_ids": fr.n_tr_ids, "n_gt_dets": fr.up(d["n_gt_dets"]),
+            "n_tr_dets": fr.up(d["n_tr_dets"]), "potential": acc["potential"][:fr.cells],
+            "alignment": acc["alignment"][:fr.cells], "id_matches": acc["id_matches"][:fr.cells],
+            "matches": matches[:n_alpha * fr.cells]}
+
+
 def device_tables(packed: PackedSequences, benchmark: str = "MOT17", stream=None, timings: dict = None) -> dict:
     """``host_tables`` by the kernels of libtrack_eval_hip.so; ``packed`` holds CUDA tensors.  Launches on ``stream``
     (default: the current one).  Returns torch tensors on the device, plus the intermediate tables (``potential``,
     ``alignment``, ``matches``, ``id_matches``) of the preprocessed data.  ``timings``: a dict that receives, per
     library call, a list of (start, end) event pairs around its launches (tools/bench_eval.py)."""
-    import torch
-    from . import _track_eval_lib as L
-    dev = packed.gt_boxes.device
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev)
-    with ctx:
-        st = torch.cuda.current_stream(dev).cuda_stream
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)                  # an empty array's address
-        ptr = lambda t: t.data_ptr() if t.numel() else nothing.data_ptr()          # noqa: E731
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)           # noqa: E731
-        new = lambda n, dt, fill=None: (torch.empty(max(int(n), 1), dtype=dt, device=dev) if fill is None else
-                                        torch.full((max(int(n), 1),), fill, dtype=dt, device=dev))     # noqa: E731
-
-        def run(name, *args):
-            if timings is None:
-                return L.check(getattr(L.lib, name)(*args), name)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            L.check(getattr(L.lib, name)(*args), name)
-            b.record()
-            timings.setdefault(name, []).append((a, b))
-
-        seq_off, gt_off, tr_off = (getattr(packed, k).cpu().numpy() for k in ("seq_off", "gt_off", "tr_off"))
-        S, F = len(seq_off) - 1, len(gt_off) - 1
-        tens = {k: getattr(packed, k).contiguous() for k in PackedSequences.ARRAYS}
-
-        def similarity(gt_boxes, tr_boxes, g_off, t_off):
-            s_off = _sim_offsets(g_off, t_off)
-            sim = new(s_off[-1], torch.float64)
-            offs = up(g_off), up(t_off), up(s_off)
-            run("trackeval_similarity", ptr(gt_boxes), ptr(tr_boxes), ptr(offs[0]), ptr(offs[1]), ptr(offs[2]),
-                                               F, ptr(sim), st)
-            return sim, offs, int(s_off[-1])
-
-        def frame_max(off):
-            return int(np.diff(off).max()) if F else 0
-
-        # 1. raw similarity; one assignment per frame flags detections on distractors
-        raw_sim, (d_gt_off, d_tr_off, d_sim_off), n_raw = similarity(tens["gt_boxes"], tens["tr_boxes"], gt_off, tr_off)
-        remove = new(tens["tr_ids"].numel(), torch.int32, 0)
-        if benchmark != "MOT15" and F:
-            status = new(F, torch.int32, 0)
-            run("trackeval_preproc_match", ptr(raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off),
-                                                  ptr(tens["gt_classes"]), F, frame_max(gt_off), frame_max(tr_off),
-                                                  ptr(remove), ptr(status), st)
-            _raise_on_status(status, "preprocessing match", "frame")
-        # 2. the filters and the relabelling, on the host (small integer arrays; not hot)
-        host = PackedSequences(packed.names, seq_off, gt_off, tr_off, None, None, tens["gt_ids"].cpu().numpy(),
-                               tens["tr_ids"].cpu().numpy(), tens["gt_classes"].cpu().numpy(),
-                               tens["gt_zero_marked"].cpu().numpy())
-        keep_gt = host.gt_zero_marked != 0
-        if benchmark != "MOT15":
-            keep_gt &= host.gt_classes == PEDESTRIAN
-        d = _compact(host, keep_gt, remove[:tens["tr_ids"].numel()].cpu().numpy() == 0)
-        gt_boxes = tens["gt_boxes"][up(d["keep_gt"])].contiguous()
-        tr_boxes = tens["tr_boxes"][up(d["keep_tr"])].contiguous()
-        max_gt, max_tr = frame_max(d["gt_off"]), frame_max(d["tr_off"])
-        max_gt_ids = int(d["n_gt_ids"].max()) if S else 0
-        max_ids = int((d["n_gt_ids"] + d["n_tr_ids"]).max()) if S else 0
-        if max_ids > L.MAX_DIM:
-            raise ValueError(f"a sequence has {max_ids} ground-truth plus tracker ids: the identity assignment exceeds "
-                             f"the device limit of {L.MAX_DIM} (evaluate it on the host)")
-        # 3. the metrics on the preprocessed data
-        sim, (d_gt_off, d_tr_off, d_sim_off), _ = similarity(gt_boxes, tr_boxes, d["gt_off"], d["tr_off"])
-        gt_ids, tr_ids, d_seq_off = up(d["gt_ids"]), up(d["tr_ids"]), up(seq_off)
-        n_gt_ids, n_tr_ids = up(d["n_gt_ids"]), up(d["n_tr_ids"])
-        cell_off, gid_off, tid_off = up(d["cell_off"]), up(d["gid_off"]), up(d["tid_off"])
-        frame_seq = up(np.repeat(np.arange(S, dtype=np.int32), np.diff(seq_off)))
-        cells, n_gid, n_tid = int(d["cell_off"][-1]), int(d["gid_off"][-1]), int(d["tid_off"][-1])
-        potential, alignment = new(cells, torch.float64), new(cells, torch.float64)
-        id_matches, gt_count, tr_count = new(cells, torch.int32), new(n_gid, torch.int32), new(n_tid, torch.int32)
-        run("trackeval_accumulate", ptr(sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(gt_ids),
-                                           ptr(tr_ids), ptr(d_seq_off), S, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off),
-                                           ptr(gid_off), ptr(tid_off), max_gt, max_tr, ptr(potential), ptr(id_matches),
-                                           ptr(gt_count), ptr(tr_count), ptr(alignment), st)
-        matches = new(len(ALPHAS) * cells, torch.int32, 0)
-        tp, loc = new(F * len(ALPHAS), torch.int32), new(F * len(ALPHAS), torch.float64)
-        frame_status = new(F, torch.int32, 0)
-        alphas = np.ascontiguousarray(ALPHAS, np.float64)
-        run("trackeval_hota_match", ptr(sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(gt_ids),
-                                           ptr(tr_ids), ptr(frame_seq), F, ptr(n_tr_ids), ptr(cell_off),
-                                           ptr(alignment), alphas.ctypes.data, max_gt, max_tr, ptr(matches), ptr(tp),
-                                           ptr(loc), ptr(frame_status), st)
-        hota_tp = torch.zeros((S, len(ALPHAS)), dtype=torch.int64, device=dev)
-        hota_sums = torch.zeros((S, 4, len(ALPHAS)), dtype=torch.float64, device=dev)
-        run("trackeval_hota_reduce", ptr(d_seq_off), S, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off),
-                                            ptr(gid_off), ptr(tid_off), ptr(gt_count), ptr(tr_count), ptr(matches),
-                                            ptr(tp), ptr(loc), ptr(hota_tp), ptr(hota_sums), st)
-        clear_ints = torch.zeros((S, 8), dtype=torch.int32, device=dev)
-        motp_sum = torch.zeros(S, dtype=torch.float64, device=dev)
-        clear_status, id_status = new(S, torch.int32, 0), new(S, torch.int32, 0)
-        run("trackeval_clear", ptr(sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(gt_ids), ptr(tr_ids),
-                                      ptr(d_seq_off), S, ptr(n_gt_ids), max_gt, max_tr, max_gt_ids, ptr(clear_ints),
-                                      ptr(motp_sum), ptr(clear_status), st)
-        identity = torch.zeros((S, 2), dtype=torch.int64, device=dev)
-        run("trackeval_identity", S, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off), ptr(gid_off), ptr(tid_off),
-                                         ptr(gt_count), ptr(tr_count), ptr(id_matches), max_ids, ptr(identity),
-                                         ptr(id_status), st)
-        _raise_on_status(frame_status, "HOTA match", "frame")
-        _raise_on_status(clear_status[:S], "CLEAR", "sequence")
-        _raise_on_status(id_status[:S], "Identity", "sequence")
-        n_sim = int(d["sim_off"][-1])
-        return {"raw_similarity": raw_sim[:n_raw], "similarity": sim[:n_sim], "hota_tp": hota_tp,
-                "hota_sums": hota_sums, "clear_ints": clear_ints.long(), "motp_sum": motp_sum, "identity": identity,
-                "gt_off": d_gt_off, "tr_off": d_tr_off, "gt_ids": gt_ids, "tr_ids": tr_ids, "n_gt_ids": n_gt_ids,
-                "n_tr_ids": n_tr_ids, "n_gt_dets": up(d["n_gt_dets"]), "n_tr_dets": up(d["n_tr_dets"]),
-                "potential": potential[:cells], "alignment": alignment[:cells], "id_matches": id_matches[:cells],
-                "matches": matches[:len(ALPHAS) * cells]}
+    with _on_stream(packed.gt_boxes.device, stream):
+        return _metric_tables(device_front(packed, benchmark, _timed(timings), on_host="evaluate"))
 
 
 def _raise_on_status(status, what: str, unit: str) -> None:

@@ -22,10 +22,11 @@ all), and ``evaluation._sequence_result`` / ``combine_sequences`` make the field
 
 As in ``evaluation.py`` the definition is stated twice: on the host (numpy, scipy; the default wherever the inputs
 live) and on the GPU (memotr_amd/csrc/track_eval_bdd.hip in front of the metric kernels of track_eval.hip), which runs
-where a CUDA ``device`` is asked for; a missing library raises then.  ``tools/bench_eval_bdd.py`` measures both on a
-synthetic set of BDD100K-val size (200 sequences x 200 frames x 8 classes): on an MI355X the device path took 86 ms
-from the call to the fields (3 ms of it in the ten library calls), the host statement 61 s on one core
-(profiles/track_eval_bdd.md).  No threshold follows from that number; the host statement stays the default.
+where a CUDA ``device`` is asked for (``device_front_bdd``, which ``diagnose_bdd100k`` stands on too); a missing library
+raises then.  ``tools/bench_eval_bdd.py`` measures both on a synthetic set of BDD100K-val size (200 sequences x 200
+frames x 8 classes): on an MI355X the device path took 86 ms from the call to the fields (3 ms of it in the ten library
+calls), the host statement 61 s on one core (profiles/track_eval_bdd.md).  No threshold follows from that number; the
+host statement stays the default.
 """
 from __future__ import annotations
 
@@ -279,141 +280,92 @@ def host_tables_bdd(packed: PackedBDD) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------ the device path
-def device_tables_bdd(packed: PackedBDD, stream=None, timings: dict = None) -> dict:
-    """``host_tables_bdd`` on the GPU; ``packed`` holds CUDA tensors.  libtrack_eval_bdd_hip.so cuts the frames into
-    the problem-major layout (``bddeval_class_count``, a cumulative sum, ``bddeval_class_split``), forms the
-    similarity and flags the unmatched detections inside ignore regions (``bddeval_similarity``, ``bddeval_preproc``);
-    the kept detections then go through the metric kernels of libtrack_eval_hip.so with S * 8 sequences.  Launches on
-    ``stream`` (default: the current one); returns torch tensors on the device.  ``timings`` as ``device_tables``."""
+def device_front_bdd(packed: PackedBDD, run=None, scatter_rows: bool = False, check_ids: bool = False) -> E.DeviceFront:
+    """``_preprocess_host`` by the kernels of libtrack_eval_bdd_hip.so, on the current stream; ``packed`` holds CUDA
+    tensors.  The one statement of what ``device_tables_bdd`` and ``diagnose_bdd100k._device_rows`` start with: the
+    frames cut into the problem-major layout (``bddeval_class_count``, a cumulative sum, ``bddeval_class_split``), the
+    similarity and the unmatched detections inside ignore regions (``bddeval_similarity``, ``bddeval_preproc``), then
+    ``evaluation._front_tables`` with the S * 8 (sequence, class) pairs as its sequences.  ``run``: the per-call hook
+    every library call goes through.  ``scatter_rows``: the split carries the rows' own numbers in place of their ids,
+    which gives ``gt_src`` / ``tr_src``, and the split ids are one gather through them.  ``check_ids``: a pair whose
+    identity assignment exceeds the device limit raises.  Beside ``evaluation.DeviceFront``'s attributes the front
+    has ``split``: the input's ``seq_off`` and ``frame_src`` on the host; ``gt_off``, ``tr_off``, ``gt_ids``,
+    ``tr_ids``, ``gt_boxes``, ``tr_boxes`` of the class split and ``remove`` on the device."""
     import torch
     from . import _track_eval_bdd_lib as B
     from . import _track_eval_lib as L
-    dev = packed.gt_boxes.device
-    ctx = torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev)
-    with ctx:
-        st = torch.cuda.current_stream(dev).cuda_stream
-        nothing = torch.zeros(2, dtype=torch.float64, device=dev)                  # an empty array's address
-        ptr = lambda t: t.data_ptr() if t.numel() else nothing.data_ptr()          # noqa: E731
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)           # noqa: E731
-        new = lambda n, dt, fill=None: (torch.empty(max(int(n), 1), dtype=dt, device=dev) if fill is None else
-                                        torch.full((max(int(n), 1),), fill, dtype=dt, device=dev))     # noqa: E731
-
-        def run(module, name, *args):
-            if timings is None:
-                return module.check(getattr(module.lib, name)(*args), name)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            module.check(getattr(module.lib, name)(*args), name)
-            b.record()
-            timings.setdefault(name, []).append((a, b))
-
-        seq_off = packed.seq_off.cpu().numpy()
-        S, F = len(seq_off) - 1, len(packed.gt_off) - 1
-        P, F8 = S * N_CLASSES, F * N_CLASSES
-        tens = {k: getattr(packed, k).contiguous() for k in PackedBDD.ARRAYS}
-        NG, NT = tens["gt_ids"].numel(), tens["tr_ids"].numel()
-        split_seq_off, frame_src = _split_offsets(seq_off)
-        frame_seq = up(np.repeat(np.arange(S, dtype=np.int32), np.diff(seq_off)))
-        d_frame_src = up(frame_src)
-
-        # 1. the class split: counts per (frame, class), their running sum, the stable scatter
-        counts = torch.zeros((2, max(F8, 1)), dtype=torch.int32, device=dev)
-        if F:
-            run(B, "bddeval_class_count", ptr(tens["gt_classes"]), ptr(tens["tr_classes"]), ptr(tens["gt_off"]),
-                ptr(tens["tr_off"]), ptr(tens["seq_off"]), ptr(frame_seq), F, ptr(counts[0]), ptr(counts[1]), st)
-        offs = torch.zeros((2, F8 + 1), dtype=torch.int32, device=dev)
-        offs[:, 1:] = torch.cumsum(counts[:, :F8], 1, dtype=torch.int32)
-        d_gt_off, d_tr_off = offs[0].contiguous(), offs[1].contiguous()
-        gt_off, tr_off = d_gt_off.cpu().numpy(), d_tr_off.cpu().numpy()            # (synchronises: sizes the rest)
-        n_gt, n_tr = int(gt_off[-1]), int(tr_off[-1])
-        gt_boxes, tr_boxes = new(4 * n_gt, torch.float64), new(4 * n_tr, torch.float64)
-        gt_ids, tr_ids = new(n_gt, torch.int32), new(n_tr, torch.int32)
-        if F:
-            run(B, "bddeval_class_split", ptr(tens["gt_boxes"]), ptr(tens["tr_boxes"]), ptr(tens["gt_ids"]),
-                ptr(tens["tr_ids"]), ptr(tens["gt_classes"]), ptr(tens["tr_classes"]), ptr(tens["gt_off"]),
+    fr = E.DeviceFront(packed.gt_boxes.device, run)
+    ptr, new, entry = fr.ptr, fr.new, (B, "bddeval_similarity")
+    seq_off = packed.seq_off.cpu().numpy()
+    S, F = len(seq_off) - 1, len(packed.gt_off) - 1
+    F8 = F * N_CLASSES
+    fr.tens = tens = {k: getattr(packed, k).contiguous() for k in PackedBDD.ARRAYS}
+    split_seq_off, frame_src = _split_offsets(seq_off)
+    frame_seq = fr.up(np.repeat(np.arange(S, dtype=np.int32), np.diff(seq_off)))
+    d_frame_src = fr.up(frame_src)
+    # 1. the class split: counts per (frame, class), their running sum, the stable scatter
+    counts = torch.zeros((2, max(F8, 1)), dtype=torch.int32, device=fr.dev)
+    if F:
+        fr.call(B, "bddeval_class_count", ptr(tens["gt_classes"]), ptr(tens["tr_classes"]), ptr(tens["gt_off"]),
+                ptr(tens["tr_off"]), ptr(tens["seq_off"]), ptr(frame_seq), F, ptr(counts[0]), ptr(counts[1]))
+    offs = torch.zeros((2, F8 + 1), dtype=torch.int32, device=fr.dev)
+    offs[:, 1:] = torch.cumsum(counts[:, :F8], 1, dtype=torch.int32)
+    d_gt_off, d_tr_off = offs[0].contiguous(), offs[1].contiguous()
+    gt_off, tr_off = d_gt_off.cpu().numpy(), d_tr_off.cpu().numpy()                # (synchronises: sizes the rest)
+    n_gt, n_tr = int(gt_off[-1]), int(tr_off[-1])
+    gt_boxes, tr_boxes = new(4 * n_gt, torch.float64), new(4 * n_tr, torch.float64)
+    gt_ids, tr_ids = new(n_gt, torch.int32), new(n_tr, torch.int32)
+    if F:
+        carried = (tens["gt_ids"], tens["tr_ids"])
+        if scatter_rows:
+            carried = (torch.arange(max(tens["gt_ids"].numel(), tens["tr_ids"].numel(), 1), dtype=torch.int32,
+                                    device=fr.dev),) * 2
+        fr.call(B, "bddeval_class_split", ptr(tens["gt_boxes"]), ptr(tens["tr_boxes"]), ptr(carried[0]),
+                ptr(carried[1]), ptr(tens["gt_classes"]), ptr(tens["tr_classes"]), ptr(tens["gt_off"]),
                 ptr(tens["tr_off"]), ptr(tens["seq_off"]), ptr(frame_seq), F, ptr(d_gt_off), ptr(d_tr_off),
-                ptr(gt_boxes), ptr(tr_boxes), ptr(gt_ids), ptr(tr_ids), st)
+                ptr(gt_boxes), ptr(tr_boxes), ptr(gt_ids), ptr(tr_ids))
+    gt_ids, tr_ids = gt_ids[:n_gt], tr_ids[:n_tr]
+    fr.split = {"seq_off": seq_off, "frame_src": frame_src, "gt_off": d_gt_off, "tr_off": d_tr_off}
+    if scatter_rows:
+        fr.split["gt_src"], fr.split["tr_src"] = gt_ids.long(), tr_ids.long()
+        gt_ids, tr_ids = tens["gt_ids"][fr.split["gt_src"]], tens["tr_ids"][fr.split["tr_src"]]
+    # 2. raw similarity; one assignment per (frame, class), then the ignore regions for what stayed unmatched
+    fr.raw_sim, (_, _, d_sim_off), fr.n_raw = fr.similarity(entry, gt_boxes, tr_boxes, gt_off, tr_off)
+    remove = new(n_tr, torch.int32, 0)
+    if F8:
+        status = new(F8, torch.int32, 0)
+        fr.call(B, "bddeval_preproc", ptr(fr.raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(tr_boxes),
+                ptr(tens["ig_off"]), ptr(tens["ig_boxes"]), ptr(d_frame_src), F8, E._frame_max(gt_off),
+                E._frame_max(tr_off), ptr(remove), ptr(status))
+        E._raise_on_status(status, "preprocessing match", "(frame, class)")
+    fr.split.update(gt_ids=gt_ids, tr_ids=tr_ids, gt_boxes=gt_boxes[:4 * n_gt].view(-1, 4),
+                    tr_boxes=tr_boxes[:4 * n_tr].view(-1, 4), remove=remove[:n_tr])
 
-        def similarity(g_boxes, t_boxes, g_off, t_off):
-            s_off = E._sim_offsets(g_off, t_off)
-            sim = new(s_off[-1], torch.float64)
-            offsets = up(g_off), up(t_off), up(s_off)
-            run(B, "bddeval_similarity", ptr(g_boxes), ptr(t_boxes), ptr(offsets[0]), ptr(offsets[1]),
-                ptr(offsets[2]), F8, ptr(sim), st)
-            return sim, offsets, int(s_off[-1])
-
-        def frame_max(off):
-            return int(np.diff(off).max()) if F8 else 0
-
-        # 2. raw similarity; one assignment per (frame, class), then the ignore regions for what stayed unmatched
-        raw_sim, (_, _, d_sim_off), n_raw = similarity(gt_boxes, tr_boxes, gt_off, tr_off)
-        remove = new(n_tr, torch.int32, 0)
-        if F8:
-            status = new(F8, torch.int32, 0)
-            run(B, "bddeval_preproc", ptr(raw_sim), ptr(d_sim_off), ptr(d_gt_off), ptr(d_tr_off), ptr(tr_boxes),
-                ptr(tens["ig_off"]), ptr(tens["ig_boxes"]), ptr(d_frame_src), F8, frame_max(gt_off),
-                frame_max(tr_off), ptr(remove), ptr(status), st)
-            E._raise_on_status(status, "preprocessing match", "(frame, class)")
-        # 3. the filter and the relabelling, on the host (small integer arrays; not hot)
-        names = [f"{n}/{c}" for n in packed.names for c in CLASSES]
-        host = E.PackedSequences(names, split_seq_off, gt_off, tr_off, None, None, gt_ids[:n_gt].cpu().numpy(),
-                                 tr_ids[:n_tr].cpu().numpy(), None, None)
-        d = E._compact(host, np.ones(n_gt, bool), remove[:n_tr].cpu().numpy() == 0)
-        kept_boxes = tr_boxes[:4 * n_tr].view(-1, 4)[up(d["keep_tr"])].contiguous()
-        max_gt, max_tr = frame_max(d["gt_off"]), frame_max(d["tr_off"])
-        max_gt_ids = int(d["n_gt_ids"].max()) if P else 0
-        n_ids = d["n_gt_ids"].astype(np.int64) + d["n_tr_ids"]
-        if P and n_ids.max() > L.MAX_DIM:
+    def check(n_ids):
+        if check_ids and E._most(n_ids) > L.MAX_DIM:
             p = int(n_ids.argmax())
             raise ValueError(f"sequence {packed.names[p // N_CLASSES]}, class {CLASSES[p % N_CLASSES]}: "
                              f"{int(n_ids[p])} ground-truth plus tracker ids: the identity assignment exceeds the "
                              f"device limit of {L.MAX_DIM} (evaluate it on the host)")
-        max_ids = int(n_ids.max()) if P else 0
-        # 4. the metrics on the preprocessed data, S * 8 sequences
-        sim, (k_gt_off, k_tr_off, k_sim_off), n_sim = similarity(gt_boxes, kept_boxes, d["gt_off"], d["tr_off"])
-        k_gt_ids, k_tr_ids, d_seq_off = up(d["gt_ids"]), up(d["tr_ids"]), up(split_seq_off)
-        n_gt_ids, n_tr_ids = up(d["n_gt_ids"]), up(d["n_tr_ids"])
-        cell_off, gid_off, tid_off = up(d["cell_off"]), up(d["gid_off"]), up(d["tid_off"])
-        split_frame_seq = up(np.repeat(np.arange(P, dtype=np.int32), np.diff(split_seq_off)))
-        cells, n_gid, n_tid = int(d["cell_off"][-1]), int(d["gid_off"][-1]), int(d["tid_off"][-1])
-        potential, alignment = new(cells, torch.float64), new(cells, torch.float64)
-        id_matches, gt_count, tr_count = new(cells, torch.int32), new(n_gid, torch.int32), new(n_tid, torch.int32)
-        run(L, "trackeval_accumulate", ptr(sim), ptr(k_sim_off), ptr(k_gt_off), ptr(k_tr_off), ptr(k_gt_ids),
-            ptr(k_tr_ids), ptr(d_seq_off), P, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off), ptr(gid_off), ptr(tid_off),
-            max_gt, max_tr, ptr(potential), ptr(id_matches), ptr(gt_count), ptr(tr_count), ptr(alignment), st)
-        matches = new(len(ALPHAS) * cells, torch.int32, 0)
-        tp, loc = new(F8 * len(ALPHAS), torch.int32), new(F8 * len(ALPHAS), torch.float64)
-        frame_status = new(F8, torch.int32, 0)
-        alphas = np.ascontiguousarray(ALPHAS, np.float64)
-        run(L, "trackeval_hota_match", ptr(sim), ptr(k_sim_off), ptr(k_gt_off), ptr(k_tr_off), ptr(k_gt_ids),
-            ptr(k_tr_ids), ptr(split_frame_seq), F8, ptr(n_tr_ids), ptr(cell_off), ptr(alignment), alphas.ctypes.data,
-            max_gt, max_tr, ptr(matches), ptr(tp), ptr(loc), ptr(frame_status), st)
-        hota_tp = torch.zeros((P, len(ALPHAS)), dtype=torch.int64, device=dev)
-        hota_sums = torch.zeros((P, 4, len(ALPHAS)), dtype=torch.float64, device=dev)
-        run(L, "trackeval_hota_reduce", ptr(d_seq_off), P, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off), ptr(gid_off),
-            ptr(tid_off), ptr(gt_count), ptr(tr_count), ptr(matches), ptr(tp), ptr(loc), ptr(hota_tp), ptr(hota_sums),
-            st)
-        clear_ints = torch.zeros((P, 8), dtype=torch.int32, device=dev)
-        motp_sum = torch.zeros(P, dtype=torch.float64, device=dev)
-        clear_status, id_status = new(P, torch.int32, 0), new(P, torch.int32, 0)
-        run(L, "trackeval_clear", ptr(sim), ptr(k_sim_off), ptr(k_gt_off), ptr(k_tr_off), ptr(k_gt_ids),
-            ptr(k_tr_ids), ptr(d_seq_off), P, ptr(n_gt_ids), max_gt, max_tr, max_gt_ids, ptr(clear_ints),
-            ptr(motp_sum), ptr(clear_status), st)
-        identity = torch.zeros((P, 2), dtype=torch.int64, device=dev)
-        run(L, "trackeval_identity", P, ptr(n_gt_ids), ptr(n_tr_ids), ptr(cell_off), ptr(gid_off), ptr(tid_off),
-            ptr(gt_count), ptr(tr_count), ptr(id_matches), max_ids, ptr(identity), ptr(id_status), st)
-        E._raise_on_status(frame_status, "HOTA match", "(frame, class)")
-        E._raise_on_status(clear_status[:P], "CLEAR", "(sequence, class)")
-        E._raise_on_status(id_status[:P], "Identity", "(sequence, class)")
-        return {"raw_similarity": raw_sim[:n_raw], "similarity": sim[:n_sim], "hota_tp": hota_tp,
-                "hota_sums": hota_sums, "clear_ints": clear_ints.long(), "motp_sum": motp_sum, "identity": identity,
-                "gt_off": k_gt_off, "tr_off": k_tr_off, "gt_ids": k_gt_ids, "tr_ids": k_tr_ids, "n_gt_ids": n_gt_ids,
-                "n_tr_ids": n_tr_ids, "n_gt_dets": up(d["n_gt_dets"]), "n_tr_dets": up(d["n_tr_dets"]),
-                "split_gt_off": d_gt_off, "split_tr_off": d_tr_off, "split_gt_ids": gt_ids[:n_gt],
-                "split_tr_ids": tr_ids[:n_tr], "split_gt_boxes": gt_boxes[:4 * n_gt].view(-1, 4),
-                "split_tr_boxes": tr_boxes[:4 * n_tr].view(-1, 4), "tr_remove": remove[:n_tr],
-                "potential": potential[:cells], "alignment": alignment[:cells], "id_matches": id_matches[:cells],
-                "matches": matches[:len(ALPHAS) * cells]}
+
+    # 3. the filter and the relabelling on the host, the similarity of what is kept: all ground truth stays
+    host = _as_sequences(packed.names, {"seq_off": split_seq_off, "gt_off": gt_off, "tr_off": tr_off,
+                                        "gt_ids": gt_ids.cpu().numpy(), "tr_ids": tr_ids.cpu().numpy()})
+    return E._front_tables(fr, entry, host, None, fr.split["remove"].cpu().numpy() == 0, gt_boxes,
+                           fr.split["tr_boxes"], check)
+
+
+def device_tables_bdd(packed: PackedBDD, stream=None, timings: dict = None) -> dict:
+    """``host_tables_bdd`` on the GPU; ``packed`` holds CUDA tensors.  ``device_front_bdd`` cuts the frames into the
+    problem-major layout and preprocesses them; the kept detections then go through ``evaluation._metric_tables``, the
+    metric kernels of libtrack_eval_hip.so, with S * 8 sequences.  Launches on ``stream`` (default: the current one);
+    returns torch tensors on the device.  ``timings`` as ``device_tables``."""
+    with E._on_stream(packed.gt_boxes.device, stream):
+        fr = device_front_bdd(packed, E._timed(timings), check_ids=True)
+        out = E._metric_tables(fr, "(frame, class)", "(sequence, class)")
+        out.update({"split_" + k: fr.split[k] for k in ("gt_off", "tr_off", "gt_ids", "tr_ids", "gt_boxes", "tr_boxes")},
+                   tr_remove=fr.split["remove"])
+        return out
 
 
 # ------------------------------------------------------------------------------------------- tables -> the fields
